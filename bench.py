@@ -7,14 +7,18 @@ stride 4096, random bytes; one step = one crc32c_batch() over the whole batch
 config 4 at N = 8: 8 Mi items), so per-GPU work is fixed ("scaling": "weak");
 the ranks share nothing but the timing barrier (no data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Rank 0 prints one JSON line.  `value` = all ranks' bytes / max-over-ranks time.
-`roofline.achieved` = algorithmic bytes per launch (sum of span lengths) / the
-average kernel duration measured with HIP events on the launch stream.
-`cpu_baseline` = the reference crc32c.c (compiled under oracle/_ref) on the
-host cores, rank 0, on a bounded sample of the same items; its CRCs are also
+A plain run sets up, warms up, times the K steps and prints one JSON line
+(rank 0).  `value` = all ranks' bytes / max-over-ranks time; `ms_per_step` =
+that time / K.  `roofline.achieved` = algorithmic bytes per launch (sum of
+span lengths) / the average kernel duration measured with HIP events around
+the timed launches.
+`--dump-outputs DIR` writes the CRCs of the last timed step as DIR/<name>.npy
+(see dump_outputs).
+`--full` adds `cpu_baseline` = the reference crc32c.c (compiled under
+oracle/_ref) on the host cores, rank 0, over the same items; its CRCs are also
 compared with the GPU's for those items.
 """
 from __future__ import annotations
@@ -155,6 +159,26 @@ def settle(step, ms: float) -> int:
         torch.cuda.synchronize()
         n += 8
     return n
+
+
+DUMP_MAX_BYTES = 60_000_000  # all files of one --dump-outputs run (headers included) stay below 64 MB
+
+
+def dump_outputs(dirname: str, outs: dict, shares: int = 1):
+    """--dump-outputs: write each tensor of `outs` (name -> the int32 CRC
+    tensor the timed path filled in its last step) as DIR/<name>.npy, the
+    CRCs as unsigned values in float64 (exact).  `shares` = the number of
+    files the whole run writes (ranks x tensors); a tensor larger than its
+    share of DUMP_MAX_BYTES is cut to a fixed sample (sorted indices drawn
+    without replacement by numpy's default_rng(0))."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES // 8 // max(shares, len(outs))
+    for name, out in outs.items():
+        crc = out.cpu().numpy().view(np.uint32)
+        if crc.size > budget:
+            crc = crc[np.sort(np.random.default_rng(0).choice(crc.size, budget, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), crc.astype(np.float64))
 
 
 def cpu_topology():
@@ -452,7 +476,13 @@ def main(argv=None):
                     help="before the warmup steps, repeat the step for this long (wall ms) so the GPU clock "
                          "leaves its idle ramp; not counted as warmup or timed steps (0 = off)")
     ap.add_argument("--items", type=int, default=ITEMS_PER_GPU, help="items per GPU (default: config 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what is not needed for it: the reference CPU baseline "
+                         "and its CRC comparison with the GPU's (`cpu_baseline` in the result line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the CRCs of the last timed step as DIR/<name>.npy "
+                         "(headline workload only)")
     ap.add_argument("--events", default="region", choices=["region", "launch"],
                     help="HIP events around the timed launches (region) or around each launch")
     ap.add_argument("--fill", default="splitmix", choices=["splitmix", "randint"],
@@ -465,10 +495,12 @@ def main(argv=None):
     ap.add_argument("--span-len", type=int, default=4133, help="config2r: span length (stride = len + 32)")
     args = ap.parse_args(argv)
     if args.workload != "config2":
+        if args.dump_outputs:
+            ap.error("--dump-outputs writes the headline workload's outputs (--workload config2)")
         return extra_workload(args)
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # no launcher: one process drives the N devices itself
-        return headline_devices(args)
+        return headline_devices(args, args.dump_outputs) if args.dump_outputs else headline_devices(args)
 
     rank, world, local = dist_setup(args.gpus)
     if _lib.lib.crc32c_gpu_count() < 1:
@@ -482,6 +514,7 @@ def main(argv=None):
     settled = settle(lambda k: run_steps(spans, k, stream), args.settle_ms)
     for a, b in run_steps(spans, max(1, args.warmup), stream):
         pass
+    out.zero_()  # (what is left after the timed steps is theirs, not the warmup's)
     torch.cuda.synchronize()
 
     per_launch = args.events == "launch"
@@ -493,7 +526,9 @@ def main(argv=None):
 
     result = headline_result(args, value, elapsed, kernel_ms, world, settled,
                              f"items sharded across {world} rank(s), no collective on the data path")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # the CPU leg runs at N = 1 only
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"crc32c" if world == 1 else f"crc32c_rank{rank}": out}, world)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:  # the CPU leg runs at N = 1 only
         result["cpu_baseline"] = cpu_baseline(data, out)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -540,14 +575,15 @@ def headline_result(args, value, elapsed, kernel_ms, n_gpus, settled, parallelis
     }
 
 
-def headline_devices(args):
+def headline_devices(args, dump_dir=None):
     """The headline on --gpus N devices from ONE process (bench.py started
     without a launcher, WORLD_SIZE unset): device g holds its own 1 Mi x 4 KiB
     shard (seed 42 + g, as rank g would) and K1 runs on every device, each on
     its own stream, the K launches of all devices enqueued before any is
     waited for.  The timed region is bracketed by a synchronize of every
     device; value = all devices' bytes / that wall time, kernel_ms = the
-    slowest device's average launch.  No data-path collective, as with ranks."""
+    slowest device's average launch.  No data-path collective, as with ranks.
+    With `dump_dir`, device g's CRCs of the last step go to crc32c_gpu<g>.npy."""
     ng = args.gpus
     vis = torch.cuda.device_count()  # (does not initialise the GPU)
     if vis < ng:
@@ -578,11 +614,16 @@ def headline_devices(args):
     settled = settle(lambda k: (launch(k), sync_all()), args.settle_ms)
     launch(max(1, args.warmup))
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ng)]
+    for g, data, out, sp, st in devs:
+        with torch.cuda.stream(st):
+            out.zero_()  # (what is left after the timed steps is theirs, not the warmup's)
     sync_all()
     t0 = time.perf_counter()
     launch(args.steps, evs)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(dump_dir, {f"crc32c_gpu{g}": out for g, data, out, sp, st in devs})
     kms = [evs[g][0].elapsed_time(evs[g][1]) / args.steps for g in range(ng)]
     value = ng * args.items * ITEM_BYTES * args.steps / elapsed / 2**30
     result = headline_result(args, value, elapsed, max(kms), ng, settled,

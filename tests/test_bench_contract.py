@@ -65,6 +65,62 @@ def test_cpu_baseline_runs_the_reference_on_every_core(monkeypatch):
     assert r["value"] == max(r["numa_local"], r["resident"])
 
 
+def test_dump_outputs_writes_exact_float64_crcs(tmp_path):
+    """--dump-outputs: one .npy per output, the CRCs as unsigned values in
+    float64 (exact up to 2^32 - 1)."""
+    import torch
+    crc = np.array([0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF, 0xE3069283], np.uint32)
+    bench.dump_outputs(str(tmp_path / "d"), {"crc32c": torch.from_numpy(crc.view(np.int32).copy())})
+    assert os.listdir(tmp_path / "d") == ["crc32c.npy"]
+    got = np.load(tmp_path / "d" / "crc32c.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, crc.astype(np.float64))
+
+
+def test_dump_outputs_samples_what_exceeds_the_size_limit(tmp_path, monkeypatch):
+    """Outputs larger than their share of the limit are cut to a fixed sample
+    (the same indices every run), and the files together stay below it."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 1000)
+    outs = {f"crc32c_gpu{g}": torch.arange(g * 10000, g * 10000 + 3000, dtype=torch.int32) for g in range(4)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    a = [np.load(tmp_path / "a" / f"crc32c_gpu{g}.npy") for g in range(4)]
+    b = [np.load(tmp_path / "b" / f"crc32c_gpu{g}.npy") for g in range(4)]
+    assert all(x.shape == (250,) and np.array_equal(x, y) for x, y in zip(a, b))
+    assert sum(x.nbytes for x in a) <= 8 * 1000
+    for g, x in enumerate(a):  # sorted, distinct elements of that device's output
+        assert (np.diff(x) > 0).all() and x[0] >= g * 10000 and x[-1] < g * 10000 + 3000
+    assert np.array_equal(a[1] - 10000, a[0])  # the same indices on every device
+
+
+def test_the_cpu_baseline_runs_only_with_full(monkeypatch):
+    """A plain run does only what the headline needs: the CPU leg is behind
+    --full (and --no-cpu-baseline still leaves it out there)."""
+    import torch
+
+    class Stream:
+        cuda_stream = 0
+
+    out = torch.zeros(4, dtype=torch.int32)
+    calls = []
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "dist_setup", lambda n: (0, 1, 0))
+    monkeypatch.setattr(bench._lib.lib, "crc32c_gpu_count", lambda: 1, raising=False)
+    monkeypatch.setattr(bench, "make_batch", lambda n, seed, fill: (None, out, None))
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda: Stream())
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: None)
+    monkeypatch.setattr(bench, "run_steps", lambda *a, **k: [])
+    monkeypatch.setattr(bench, "timed", lambda step, steps, world: (1e-3 * steps, []))
+    monkeypatch.setattr(bench, "headline_result", lambda *a: {})
+    monkeypatch.setattr(bench, "cpu_baseline", lambda d, o: calls.append("cpu") or {})
+    bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--settle-ms", "0"])
+    assert calls == []
+    bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--full", "--no-cpu-baseline"])
+    assert calls == []
+    bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--full"])
+    assert calls == ["cpu"]
+
+
 def test_gpus_n_without_launcher_runs_in_one_process(monkeypatch):
     """`python bench.py --gpus N` (the driver's form, no torchrun) takes the
     single-process path over N devices instead of stopping in dist_setup; with

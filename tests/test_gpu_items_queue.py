@@ -341,6 +341,30 @@ def test_bench_headline_over_every_device_in_one_process(torch):
     assert res["roofline"]["frac"] > 0 and res["scaling"] == "weak"
 
 
+def test_bench_plain_run_dumps_the_last_steps_crcs(torch, tmp_path, capsys):
+    """A plain run (no --full) prints the headline line without the CPU leg
+    and, with --dump-outputs, writes the CRCs its timed path left: those of the
+    splitmix64(42) batch, equal to the oracle's, identical from run to run."""
+    import json
+
+    import bench
+    n = 3000
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--items", str(n)]
+    dumps = []
+    for d in ("a", "b"):
+        bench.main(argv + ["--dump-outputs", str(tmp_path / d)])
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "cpu_baseline" not in line
+        assert os.listdir(tmp_path / d) == ["crc32c.npy"]
+        dumps.append(np.load(tmp_path / d / "crc32c.npy"))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (n,)
+    assert np.array_equal(dumps[0], dumps[1])
+    host = bench.splitmix64_bytes(n * bench.ITEM_BYTES, 42).cpu().numpy()
+    want = oracle.batch(host, np.arange(n, dtype=np.uint64) * bench.ITEM_BYTES, np.full(n, bench.ITEM_BYTES))
+    assert np.array_equal(dumps[0], want.astype(np.float64))
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
