@@ -29,6 +29,7 @@
 #include "../../include/crc32c_batch.h"
 #include "crc32c_gf2.h"
 #include "crc32c_host.h"
+#include "grow_buf.h"
 #include "crc32c_kernels.hip"
 
 // ---------------------------------------------------------------------------
@@ -66,11 +67,40 @@ constexpr uint32_t kFixedLen = mcrc_dev::kK1Bytes;  // K1: 8 pieces x 32 lanes x
 
 thread_local float g_last_kernel_ms = -1.0f;
 
-struct Queue;
-enum {
-    kScrWalkCnt, kScrWalkPrefix, kScrWalkOffs, kScrWalkOk, kScrWalkScan, kScrStage, kScrItemOffs, kScrItemOut,
-    kScrFb, kScrFbOffs, kScrFbOk, kScrRt, kScrWalkSlots, kScrCount
+// The memory sources of the shim's grow-only buffers (grow_buf.h).  Device
+// blocks are freed with the synchronous hipFree: a regrow outlasts kernels
+// still using the old block on another stream.
+bool alloc_ok(hipError_t e) {
+    if (e != hipSuccess) (void)hipGetLastError();  // (not left pending for a later launch check)
+    return e == hipSuccess;
+}
+struct DeviceMem {
+    static bool alloc(size_t bytes, mcrc::Block *b) {
+        const bool ok = alloc_ok(hipMalloc(&b->p, bytes));
+        b->dv = b->p;
+        return ok;
+    }
+    static void free(const mcrc::Block &b) { (void)hipFree(b.p); }
 };
+struct PinnedMem {  // page-locked, for the host and the copy engines only
+    static bool alloc(size_t bytes, mcrc::Block *b) {
+        return alloc_ok(hipHostMalloc(&b->p, bytes, hipHostMallocDefault));
+    }
+    static void free(const mcrc::Block &b) { (void)hipHostFree(b.p); }
+};
+struct MappedMem : PinnedMem {  // page-locked and mapped: dev() is the address kernels use
+    static bool alloc(size_t bytes, mcrc::Block *b) {
+        if (!PinnedMem::alloc(bytes, b)) return false;
+        if (alloc_ok(hipHostGetDevicePointer(&b->dv, b->p, 0))) return true;
+        free(*b);
+        return false;
+    }
+};
+template <class T = uint8_t> using DevBuf = mcrc::GrowBuf<DeviceMem, T>;
+template <class T = uint8_t> using PinBuf = mcrc::GrowBuf<PinnedMem, T>;
+template <class T = uint8_t> using MapBuf = mcrc::GrowBuf<MappedMem, T>;
+
+struct Queue;
 
 struct Device {
     int id = -1;
@@ -79,6 +109,7 @@ struct Device {
     uint4 *img = nullptr;       // LDS table image of every table kernel (build_lds_image_span, chunk 16)
     uint32_t *tab8 = nullptr;   // byte-wise table (k_count / k_final: a span's head fragment and foreign bytes)
     uint32_t *xpow = nullptr;   // x^(8n) table (layout mcrc_dev::kXpow*)
+    uint32_t *segpow = nullptr; // rows x^i * x^(8*4096*k): k < 256, then k = 256 j
     uint32_t xm128 = 0;         // k_lines / k_fix: x^(-8 * 128)
     uint4 *zero = nullptr;      // kZeroBytes of zeros (one 4 KiB line set per CU slot)
     unsigned long long *nbad = nullptr;  // [0]: bad / out-of-range count, [1]: walk invariant failures
@@ -113,72 +144,60 @@ struct Device {
             busy_valid = true;
         }
     }
+    // Everything below is grow-only scratch (grow_buf.h), sized by the call
+    // that needs it and guarded by mu and the stream-order hand-over above.
     // host-batch staging: two device slots + two pinned slots
-    uint8_t *dbuf[2] = {nullptr, nullptr};
-    uint8_t *pin[2] = {nullptr, nullptr};
-    uint64_t slot_bytes = 0;
-    uint64_t *doffs[2] = {nullptr, nullptr};
-    uint32_t *dlens[2] = {nullptr, nullptr}, *dcin[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr};
-    uint64_t *hoffs[2] = {nullptr, nullptr};  // pinned twins of the descriptor slots
-    uint32_t *hlens[2] = {nullptr, nullptr}, *hcin[2] = {nullptr, nullptr}, *hout[2] = {nullptr, nullptr};
-    uint64_t slot_items = 0;
-    // work-unit planning for long / variable spans (grow-only)
-    uint64_t *nunit = nullptr;  // per span: units | blocks << 32
-    mcrc_dev::PlanSum *tile_sum = nullptr, *tile_pre = nullptr;  // per kPlanTile spans: sums, exclusive scan (+ total)
-    uint32_t *span_acc = nullptr, *counters = nullptr;
-    uint32_t *starts = nullptr;  // balanced plan: first record of each span-kernel group (groups + 1)
-    uint32_t *segpow = nullptr;  // rows x^i * x^(8*4096*k): k < 256, then k = 256 j
-    mcrc_dev::UnitRec *units = nullptr, *whole = nullptr;
-    uint4 *irec = nullptr;  // per-span record written by k_count
-    uint8_t *fast = nullptr;     // per span: its unit is one whole block (k_blocks takes it)
-    uint32_t *fastidx = nullptr; // the fast spans' indices, compacted (k_expand)
-    uint4 *big = nullptr;  // spans expanded by k_expand_big: {span, p0, b0}
-    uint64_t plan_items = 0, plan_units = 0;
-    // grow-only scratch for the page walk and staged item batches
-    struct Scratch {
-        void *p = nullptr;
-        size_t bytes = 0;
-    } scratch[kScrCount];
-    void *grow(int slot, size_t bytes) {
-        Scratch &s = scratch[slot];
-        if (s.bytes < bytes) {
-            if (s.p) (void)hipFree(s.p);
-            s.p = nullptr;
-            s.bytes = 0;
-            if (hipMalloc(&s.p, bytes) != hipSuccess) {
-                s.p = nullptr;
-                (void)hipGetLastError();  // (not left pending for a later launch check)
-                return nullptr;
-            }
-            s.bytes = bytes;
-        }
-        return s.p;
-    }
-    // grow-only pinned, device-mapped scratch of the host item-image calls:
-    // host address in *h, the address kernels use in *dv
-    struct Pinned {
-        void *h = nullptr, *d = nullptr;
-        size_t bytes = 0;
-    } pinned[4];
-    bool grow_pinned(int slot, size_t bytes, void **h, void **dv) {
-        Pinned &s = pinned[slot];
-        if (s.bytes < bytes) {
-            if (s.h) (void)hipHostFree(s.h);
-            s = Pinned{};
-            if (hipHostMalloc(&s.h, bytes, hipHostMallocDefault) != hipSuccess) return false;
-            if (hipHostGetDevicePointer(&s.d, s.h, 0) != hipSuccess) {
-                (void)hipHostFree(s.h);
-                s = Pinned{};
-                return false;
-            }
-            s.bytes = bytes;
-        }
-        *h = s.h;
-        *dv = s.d;
-        return true;
+    DevBuf<> dbuf[2];
+    PinBuf<> pin[2];
+    DevBuf<uint64_t> doffs[2];
+    DevBuf<uint32_t> dlens[2], dcin[2], dout[2];
+    PinBuf<uint64_t> hoffs[2];  // pinned twins of the descriptor slots
+    PinBuf<uint32_t> hlens[2], hcin[2], hout[2];
+    // work-unit planning for long / variable spans
+    DevBuf<uint64_t> nunit;  // per span: units | blocks << 32
+    DevBuf<mcrc_dev::PlanSum> tile_sum, tile_pre;  // per kPlanTile spans: sums, exclusive scan (+ total)
+    DevBuf<uint32_t> span_acc, counters;
+    DevBuf<uint32_t> starts;  // balanced plan: first record of each span-kernel group (groups + 1)
+    DevBuf<mcrc_dev::UnitRec> units, whole;
+    DevBuf<uint4> irec;  // per-span record written by k_count
+    DevBuf<uint8_t> fast;      // per span: its unit is one whole block (k_blocks takes it)
+    DevBuf<uint32_t> fastidx;  // the fast spans' indices, compacted (k_expand)
+    DevBuf<uint4> big;  // spans expanded by k_expand_big: {span, p0, b0}
+    // the page walk (counts, their scan, the slots the count pass keeps, and
+    // the results when the caller's arrays do not take them)
+    DevBuf<uint32_t> walk_cnt, walk_prefix;
+    DevBuf<uint64_t> walk_slots, walk_offs;
+    DevBuf<uint8_t> walk_ok;
+    // staged host buffers (item images, pages, a chain fold's inputs) and the
+    // staged item batches' offsets and results
+    DevBuf<> stage, item_out;
+    DevBuf<uint64_t> item_offs;
+    // launch_items: the images K5 leaves to the planned path (indices, offsets,
+    // verdicts) and a stamp's per-image records for k_fix
+    DevBuf<uint32_t> fb;
+    DevBuf<uint64_t> fb_offs;
+    DevBuf<uint8_t> fb_ok;
+    DevBuf<uint2> rt;
+    // pinned, device-mapped scratch of the host item-image calls
+    MapBuf<> pin_stage, pin_ok;
+    MapBuf<uint64_t> pin_offs;
+    MapBuf<uint32_t> pin_crc;
+};
+
+// The device's shared scratch is the holder's on `st` until the end of its
+// scope: taken in stream order, handed on by the busy event on every exit
+// (sync: after `st` has drained, for calls whose results the host reads).
+struct Lease {
+    Device &d;
+    hipStream_t st;
+    bool sync;
+    Lease(Device &dev, hipStream_t s, bool sync_first = false) : d(dev), st(s), sync(sync_first) { d.acquire(st); }
+    Lease(const Lease &) = delete;
+    ~Lease() {
+        if (sync) (void)hipStreamSynchronize(st);
+        d.release(st);
     }
 };
-enum { kPinStage, kPinOffs, kPinOk, kPinCrc };
 
 std::mutex g_dev_mu;  // device discovery and first initialisation only
 // Device state by HIP ordinal (every visible device; only gfx950 ones are
@@ -367,7 +386,6 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 // Planned batches split their blocks evenly over the span kernel's 32-lane
 // groups (k_expand's balanced plan; round robin over units was the round-3
 // A/B baseline, profiles/r03_ablations/k2_balanced_plan_ab.jsonl).
-constexpr bool kSpanBalance = true;
 uint32_t span_groups(const Device &d) { return (uint32_t)d.cus * (mcrc_dev::kSpanBlock / 32); }
 // Rounds of the balanced plan (k_spans): one per kRoundBytes of the batch's
 // buffer, at most kMaxRounds, so the span kernel's groups stream through
@@ -382,40 +400,15 @@ uint32_t plan_rounds(const mcrc_dev::SpanArgs &a) {
 }
 
 int ensure_plan(Device &d, uint64_t n, uint64_t cap) {
-    if (d.plan_items < n) {
-        (void)hipFree(d.nunit);
-        (void)hipFree(d.tile_sum);
-        (void)hipFree(d.tile_pre);
-        (void)hipFree(d.whole);
-        (void)hipFree(d.irec);
-        (void)hipFree(d.span_acc);
-        (void)hipFree(d.big);
-        (void)hipFree(d.fast);
-        (void)hipFree(d.fastidx);
-        d.plan_items = 0;
-        const uint64_t ntiles = (n + mcrc_dev::kPlanTile - 1) / mcrc_dev::kPlanTile;
-        if (hipMalloc(&d.nunit, n * 8) != hipSuccess ||
-            hipMalloc(&d.tile_sum, ntiles * sizeof(mcrc_dev::PlanSum)) != hipSuccess ||
-            hipMalloc(&d.tile_pre, (ntiles + 1) * sizeof(mcrc_dev::PlanSum)) != hipSuccess ||
-            hipMalloc(&d.whole, n * sizeof(mcrc_dev::UnitRec)) != hipSuccess ||
-            hipMalloc(&d.irec, n * sizeof(uint4)) != hipSuccess || hipMalloc(&d.span_acc, n * 4) != hipSuccess ||
-            hipMalloc(&d.big, n * sizeof(uint4)) != hipSuccess || hipMalloc(&d.fast, n) != hipSuccess ||
-            hipMalloc(&d.fastidx, n * 4) != hipSuccess)
-            return CRC32C_ENOMEM;
-        d.plan_items = n;
-    }
-    if (d.plan_units < cap) {
-        (void)hipFree(d.units);
-        d.plan_units = 0;
-        // (+ one record per share boundary of the balanced plan)
-        if (hipMalloc(&d.units, (cap + (uint64_t)kMaxRounds * span_groups(d)) * sizeof(mcrc_dev::UnitRec)) != hipSuccess)
-            return CRC32C_ENOMEM;
-        d.plan_units = cap;
-    }
-    if (!d.counters && hipMalloc(&d.counters, 16) != hipSuccess) return CRC32C_ENOMEM;
-    if (!d.starts && hipMalloc(&d.starts, ((uint64_t)kMaxRounds * span_groups(d) + 1) * 4) != hipSuccess)
-        return CRC32C_ENOMEM;
-    return CRC32C_OK;
+    const uint64_t ntiles = (n + mcrc_dev::kPlanTile - 1) / mcrc_dev::kPlanTile;
+    const uint64_t shares = (uint64_t)kMaxRounds * span_groups(d);  // (one more unit record per share boundary)
+    const bool ok = d.nunit.reserve(n * 8) && d.tile_sum.reserve(ntiles * sizeof(mcrc_dev::PlanSum)) &&
+                    d.tile_pre.reserve((ntiles + 1) * sizeof(mcrc_dev::PlanSum)) &&
+                    d.whole.reserve(n * sizeof(mcrc_dev::UnitRec)) && d.irec.reserve(n * sizeof(uint4)) &&
+                    d.span_acc.reserve(n * 4) && d.big.reserve(n * sizeof(uint4)) && d.fast.reserve(n) &&
+                    d.fastidx.reserve(n * 4) && d.units.reserve((cap + shares) * sizeof(mcrc_dev::UnitRec)) &&
+                    d.counters.reserve(16) && d.starts.reserve((shares + 1) * 4);
+    return ok ? CRC32C_OK : CRC32C_ENOMEM;
 }
 
 // Every span of `len` bytes is one whole block at its G1 (mcrc_dev::one_block)
@@ -568,52 +561,54 @@ int launch_units(Device &d, mcrc_dev::SpanArgs a, hipStream_t st, Path path) {
     const uint64_t cap = plan_cap(a);
     int rc = ensure_plan(d, n, cap);
     if (rc) return rc;
-    uint32_t *nvalid = d.counters, *nwhole = d.counters + 1, *nbig = d.counters + 2;
+    uint32_t *nvalid = d.counters.get(), *nwhole = nvalid + 1, *nbig = nvalid + 2;
+    uint64_t *const nunit = d.nunit.get();
+    uint4 *const irec = d.irec.get();
+    uint8_t *const fast = d.fast.get();
+    uint32_t *const starts = d.starts.get();
+    mcrc_dev::UnitRec *const units = d.units.get();
     HIP_OK(hipMemsetAsync(nvalid, 0, 12, st));  // nvalid, nwhole, nbig
     // the balanced plan's shares: rounds x the span kernel's groups
-    const uint32_t rounds = kSpanBalance ? plan_rounds(a) : 1u;
+    const uint32_t rounds = plan_rounds(a);
     const uint32_t shares = rounds * span_groups(d);
-    if (kSpanBalance) HIP_OK(hipMemsetAsync(d.starts, 0xff, ((uint64_t)shares + 1) * 4, st));
-    a.span_acc = d.span_acc;
-    if (!path.counted)
-        hipLaunchKernelGGL((mcrc_dev::k_count<MODE>), dim3(g1), dim3(256), 0, st, a, d.nunit, d.irec, d.fast);
+    HIP_OK(hipMemsetAsync(starts, 0xff, ((uint64_t)shares + 1) * 4, st));
+    a.span_acc = d.span_acc.get();
+    if (!path.counted) hipLaunchKernelGGL((mcrc_dev::k_count<MODE>), dim3(g1), dim3(256), 0, st, a, nunit, irec, fast);
     // prefix sums of the plan (units, blocks, one-block spans): tile sums, one
     // workgroup over them, then each tile rescanned where k_expand uses it
     const uint64_t ntiles = (n + mcrc_dev::kPlanTile - 1) / mcrc_dev::kPlanTile;
     const int gt = (int)std::min<uint64_t>(ntiles, 4096);
     // (a.dn: n is the list's upper bound and its length is read on the device)
-    hipLaunchKernelGGL(mcrc_dev::k_plan_tiles, dim3(gt), dim3(mcrc_dev::kPlanThreads), 0, st,
-                       (const uint64_t *)d.nunit, (const uint8_t *)d.fast, n, a.dn, d.tile_sum);
-    mcrc_dev::PlanSum *total = d.tile_pre + ntiles;
+    mcrc_dev::PlanSum *const tile_pre = d.tile_pre.get(), *const total = tile_pre + ntiles;
+    hipLaunchKernelGGL(mcrc_dev::k_plan_tiles, dim3(gt), dim3(mcrc_dev::kPlanThreads), 0, st, (const uint64_t *)nunit,
+                       (const uint8_t *)fast, n, a.dn, d.tile_sum.get());
     hipLaunchKernelGGL(mcrc_dev::k_plan_scan, dim3(1), dim3(mcrc_dev::kPlanThreads), 0, st,
-                       (const mcrc_dev::PlanSum *)d.tile_sum, n, a.dn, d.tile_pre, total);
+                       (const mcrc_dev::PlanSum *)d.tile_sum.get(), n, a.dn, tile_pre, total);
     const uint32_t *nfast = &total->fast;
-    uint32_t *const starts = kSpanBalance ? d.starts : nullptr;
-    hipLaunchKernelGGL(mcrc_dev::k_expand, dim3(gt), dim3(mcrc_dev::kPlanThreads), 0, st, a.base,
-                       (const uint64_t *)d.nunit, (const uint8_t *)d.fast, (const mcrc_dev::PlanSum *)d.tile_pre,
-                       (const mcrc_dev::PlanSum *)total, (const uint4 *)d.irec, n, a.dn, d.units, cap, nvalid, d.whole,
-                       nwhole, d.big, nbig, d.fastidx, shares, starts);
-    hipLaunchKernelGGL(mcrc_dev::k_expand_big, dim3(1024), dim3(256), 0, st, a.base, (const uint64_t *)d.nunit,
-                       (const mcrc_dev::PlanSum *)total, (const uint4 *)d.irec, d.units, (const uint4 *)d.big,
+    hipLaunchKernelGGL(mcrc_dev::k_expand, dim3(gt), dim3(mcrc_dev::kPlanThreads), 0, st, a.base, (const uint64_t *)nunit,
+                       (const uint8_t *)fast, (const mcrc_dev::PlanSum *)tile_pre, (const mcrc_dev::PlanSum *)total,
+                       (const uint4 *)irec, n, a.dn, units, cap, nvalid, d.whole.get(), nwhole, d.big.get(), nbig,
+                       d.fastidx.get(), shares, starts);
+    hipLaunchKernelGGL(mcrc_dev::k_expand_big, dim3(1024), dim3(256), 0, st, a.base, (const uint64_t *)nunit,
+                       (const mcrc_dev::PlanSum *)total, (const uint4 *)irec, units, (const uint4 *)d.big.get(),
                        (const uint32_t *)nbig, n, a.dn, shares, starts);
     mcrc_dev::SpanArgs u = a;
-    u.units = d.units;
+    u.units = units;
     u.nunits = nvalid;
-    u.span_acc = d.span_acc;
     u.segpow = d.segpow;
     u.starts = starts;
     u.rounds = rounds;
     // spans whose unit is one whole block: k_blocks over the compacted list;
     // the other spans' units: the span kernel
     hipLaunchKernelGGL((mcrc_dev::k_blocks<false, true>), dim3(grid_for(d, n)), dim3(1024), mcrc_dev::kLdsImageK1Bytes, st,
-                       u, d.img, (const uint4 *)d.irec, (const uint32_t *)d.fastidx, (const uint32_t *)nfast);
+                       u, d.img, (const uint4 *)irec, (const uint32_t *)d.fastidx.get(), (const uint32_t *)nfast);
     spans(u, d.cus);
     mcrc_dev::SpanArgs w = u;  // (every table pointer set, even those whole units do not use)
-    w.units = d.whole;
+    w.units = d.whole.get();
     w.nunits = nwhole;
     w.starts = nullptr;
     spans(w, d.cus);
-    hipLaunchKernelGGL((mcrc_dev::k_final<MODE, true>), dim3(gf), dim3(256), 0, st, u, d.irec);
+    hipLaunchKernelGGL((mcrc_dev::k_final<MODE, true>), dim3(gf), dim3(256), 0, st, u, irec);
     HIP_OK(hipGetLastError());
     return CRC32C_OK;
 }
@@ -628,12 +623,12 @@ int launch_items(Device &d, mcrc_dev::SpanArgs a, hipStream_t st) {
     const uint64_t n = a.n;
     if (n >= 0xffffffffull) return CRC32C_EINVAL;
     mcrc_dev::ItemsOut io{};
-    io.fb = (uint32_t *)d.grow(kScrFb, n * 4);
+    io.fb = d.fb.reserve(n * 4);
     io.nfb = d.nfb;
     io.route = d.route;
-    if (MODE == 2) io.rt = (uint2 *)d.grow(kScrRt, n * 8);
-    uint64_t *fo = (uint64_t *)d.grow(kScrFbOffs, n * 8);
-    uint8_t *fok = (uint8_t *)d.grow(kScrFbOk, n);
+    if (MODE == 2) io.rt = d.rt.reserve(n * 8);
+    uint64_t *fo = d.fb_offs.reserve(n * 8);
+    uint8_t *fok = d.fb_ok.reserve(n);
     if (!io.fb || (MODE == 2 && !io.rt) || !fo || !fok) return CRC32C_ENOMEM;
     HIP_OK(hipMemsetAsync(d.nfb, 0, 4, st));
     hipLaunchKernelGGL(mcrc_dev::k_census<MODE>, dim3(1), dim3(mcrc_dev::kCensus), 0, st, a, d.route);
@@ -697,8 +692,22 @@ bool fixed_spans_fit(const crc32c_spans &s) {
     return (s.n - 1) <= (s.base_bytes - s.len) / s.stride;
 }
 
-mcrc_dev::SpanArgs span_args(const Device &d, const crc32c_spans &s) {
+// The fields every batch shares: the device's tables and the counter of bad
+// or out-of-range spans (the device's, or the coalescing queue's own); 4-B
+// client flags unless the caller says otherwise.
+mcrc_dev::SpanArgs common_args(const Device &d, unsigned long long *nbad = nullptr) {
     mcrc_dev::SpanArgs a{};
+    a.nbad = nbad ? nbad : d.nbad;
+    a.segpow = d.segpow;
+    a.xpow = d.xpow;
+    a.tab8 = d.tab8;
+    a.zero = d.zero;
+    a.cfl = 4;
+    return a;
+}
+
+mcrc_dev::SpanArgs span_args(const Device &d, const crc32c_spans &s) {
+    mcrc_dev::SpanArgs a = common_args(d);
     a.base = (const uint8_t *)s.base;
     a.base_bytes = s.base_bytes;
     a.offsets = s.offsets;
@@ -707,13 +716,7 @@ mcrc_dev::SpanArgs span_args(const Device &d, const crc32c_spans &s) {
     a.len = s.len;
     a.crc_in = s.crc_in;
     a.out = s.out;
-    a.nbad = d.nbad;  // spans outside the buffer
     a.n = s.n;
-    a.segpow = d.segpow;
-    a.xpow = d.xpow;
-    a.tab8 = d.tab8;
-    a.zero = d.zero;
-    a.cfl = 4;
     return a;
 }
 
@@ -834,37 +837,13 @@ uint64_t span_off(const crc32c_spans &s, uint64_t i) { return s.offsets ? s.offs
 uint64_t span_len(const crc32c_spans &s, uint64_t i) { return s.lens ? s.lens[i] : s.len; }
 
 int ensure_slots(Device &d, uint64_t bytes, uint64_t items) {
-    if (d.slot_bytes < bytes) {
-        for (int k = 0; k < 2; ++k) {
-            if (d.dbuf[k]) (void)hipFree(d.dbuf[k]);
-            if (d.pin[k]) (void)hipHostFree(d.pin[k]);
-            d.dbuf[k] = nullptr;
-            d.pin[k] = nullptr;
-            if (hipMalloc(&d.dbuf[k], bytes) != hipSuccess) return CRC32C_ENOMEM;
-            if (hipHostMalloc(&d.pin[k], bytes, hipHostMallocDefault) != hipSuccess) return CRC32C_ENOMEM;
-        }
-        d.slot_bytes = bytes;
-    }
-    if (d.slot_items < items) {
-        for (int k = 0; k < 2; ++k) {
-            (void)hipFree(d.doffs[k]);
-            (void)hipFree(d.dlens[k]);
-            (void)hipFree(d.dcin[k]);
-            (void)hipFree(d.dout[k]);
-            (void)hipHostFree(d.hoffs[k]);
-            (void)hipHostFree(d.hlens[k]);
-            (void)hipHostFree(d.hcin[k]);
-            (void)hipHostFree(d.hout[k]);
-            if (hipMalloc(&d.doffs[k], items * 8) != hipSuccess || hipMalloc(&d.dlens[k], items * 4) != hipSuccess ||
-                hipMalloc(&d.dcin[k], items * 4) != hipSuccess || hipMalloc(&d.dout[k], items * 4) != hipSuccess ||
-                hipHostMalloc(&d.hoffs[k], items * 8, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc(&d.hlens[k], items * 4, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc(&d.hcin[k], items * 4, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc(&d.hout[k], items * 4, hipHostMallocDefault) != hipSuccess)
-                return CRC32C_ENOMEM;
-        }
-        d.slot_items = items;
-    }
+    for (int k = 0; k < 2; ++k)
+        if (!d.dbuf[k].reserve(bytes) || !d.pin[k].reserve(bytes)) return CRC32C_ENOMEM;
+    for (int k = 0; k < 2; ++k)
+        if (!d.doffs[k].reserve(items * 8) || !d.dlens[k].reserve(items * 4) || !d.dcin[k].reserve(items * 4) ||
+            !d.dout[k].reserve(items * 4) || !d.hoffs[k].reserve(items * 8) || !d.hlens[k].reserve(items * 4) ||
+            !d.hcin[k].reserve(items * 4) || !d.hout[k].reserve(items * 4))
+            return CRC32C_ENOMEM;
     return CRC32C_OK;
 }
 
@@ -904,27 +883,25 @@ int run_host_batch(Device &d, const crc32c_spans &s) {
     auto idx = [&](uint64_t k) { return order.empty() ? k : order[k]; };
     int rc = ensure_slots(d, kSlotBytes, kSlotItems);
     if (rc) return rc;
-    d.acquire(d.stream);
-    d.acquire(d.copy);
     // Every exit waits for both streams (an H2D copy may still be reading the
-    // caller's pinned buffer after an error) and hands the scratch on.
-    struct Guard {
-        Device &d;
-        ~Guard() {
-            (void)hipStreamSynchronize(d.copy);
-            (void)hipStreamSynchronize(d.stream);
-            d.release(d.stream);
-        }
-    } guard{d};
+    // caller's pinned buffer after an error): the copy stream first, then the
+    // lease drains the library stream and hands the scratch on.
+    Lease lease(d, d.stream, true);
+    d.acquire(d.copy);
+    struct DrainCopy {
+        hipStream_t copy;
+        ~DrainCopy() { (void)hipStreamSynchronize(copy); }
+    } drain_copy{d.copy};
     const bool src_pinned = is_pinned_or_device(s.base, s.base_bytes);
     const uint8_t *src = (const uint8_t *)s.base;
     uint64_t pend_k0[2] = {0, 0}, pend_n[2] = {0, 0};  // results waiting in hout[slot]
     auto drain = [&](int k) -> int {
         if (!pend_n[k]) return CRC32C_OK;
         HIP_OK(hipEventSynchronize(d.done[k]));
-        if (order.empty()) memcpy(s.out + pend_k0[k], d.hout[k], pend_n[k] * 4);
+        const uint32_t *hout = d.hout[k].get();
+        if (order.empty()) memcpy(s.out + pend_k0[k], hout, pend_n[k] * 4);
         else
-            for (uint64_t i = 0; i < pend_n[k]; ++i) s.out[order[pend_k0[k] + i]] = d.hout[k][i];
+            for (uint64_t i = 0; i < pend_n[k]; ++i) s.out[order[pend_k0[k] + i]] = hout[i];
         pend_n[k] = 0;
         return CRC32C_OK;
     };
@@ -943,32 +920,34 @@ int run_host_batch(Device &d, const crc32c_spans &s) {
         if ((rc = drain(slot))) return rc;  // slot free: its kernel and D2H are done
         const uint8_t *h2d_src = src + lo;
         if (!src_pinned) {
-            memcpy(d.pin[slot], src + lo, bytes);
-            h2d_src = d.pin[slot];
+            memcpy(d.pin[slot].get(), src + lo, bytes);
+            h2d_src = d.pin[slot].get();
         }
+        uint64_t *const hoffs = d.hoffs[slot].get();
+        uint32_t *const hlens = d.hlens[slot].get(), *const hcin = d.hcin[slot].get();
         for (uint64_t i = 0; i < cnt; ++i) {
             const uint64_t c = idx(k0 + i);
-            d.hoffs[slot][i] = span_off(s, c) - lo;
-            if (s.lens) d.hlens[slot][i] = s.lens[c];
-            if (s.crc_in) d.hcin[slot][i] = s.crc_in[c];
+            hoffs[i] = span_off(s, c) - lo;
+            if (s.lens) hlens[i] = s.lens[c];
+            if (s.crc_in) hcin[i] = s.crc_in[c];
         }
-        HIP_OK(hipMemcpyAsync(d.dbuf[slot], h2d_src, bytes, hipMemcpyHostToDevice, d.copy));
-        HIP_OK(hipMemcpyAsync(d.doffs[slot], d.hoffs[slot], cnt * 8, hipMemcpyHostToDevice, d.copy));
-        if (s.lens) HIP_OK(hipMemcpyAsync(d.dlens[slot], d.hlens[slot], cnt * 4, hipMemcpyHostToDevice, d.copy));
-        if (s.crc_in) HIP_OK(hipMemcpyAsync(d.dcin[slot], d.hcin[slot], cnt * 4, hipMemcpyHostToDevice, d.copy));
+        crc32c_spans sub{};
+        sub.base = d.dbuf[slot].get();
+        sub.base_bytes = bytes;
+        sub.offsets = d.doffs[slot].get();
+        sub.lens = s.lens ? d.dlens[slot].get() : nullptr;
+        sub.len = s.len;
+        sub.crc_in = s.crc_in ? d.dcin[slot].get() : nullptr;
+        sub.out = d.dout[slot].get();
+        sub.n = cnt;
+        HIP_OK(hipMemcpyAsync(d.dbuf[slot].get(), h2d_src, bytes, hipMemcpyHostToDevice, d.copy));
+        HIP_OK(hipMemcpyAsync(d.doffs[slot].get(), hoffs, cnt * 8, hipMemcpyHostToDevice, d.copy));
+        if (s.lens) HIP_OK(hipMemcpyAsync(d.dlens[slot].get(), hlens, cnt * 4, hipMemcpyHostToDevice, d.copy));
+        if (s.crc_in) HIP_OK(hipMemcpyAsync(d.dcin[slot].get(), hcin, cnt * 4, hipMemcpyHostToDevice, d.copy));
         HIP_OK(hipEventRecord(d.copied[slot], d.copy));
         HIP_OK(hipStreamWaitEvent(d.stream, d.copied[slot], 0));
-        crc32c_spans sub{};
-        sub.base = d.dbuf[slot];
-        sub.base_bytes = bytes;
-        sub.offsets = d.doffs[slot];
-        sub.lens = s.lens ? d.dlens[slot] : nullptr;
-        sub.len = s.len;
-        sub.crc_in = s.crc_in ? d.dcin[slot] : nullptr;
-        sub.out = d.dout[slot];
-        sub.n = cnt;
         if ((rc = enqueue_device(d, sub, d.stream))) return rc;
-        HIP_OK(hipMemcpyAsync(d.hout[slot], d.dout[slot], cnt * 4, hipMemcpyDeviceToHost, d.stream));
+        HIP_OK(hipMemcpyAsync(d.hout[slot].get(), sub.out, cnt * 4, hipMemcpyDeviceToHost, d.stream));
         HIP_OK(hipEventRecord(d.done[slot], d.stream));
         pend_k0[slot] = k0;
         pend_n[slot] = cnt;
@@ -990,24 +969,18 @@ int device_batch(Device &d, const crc32c_spans &s, unsigned flags, hipStream_t s
         return fixed_spans_fit(s) ? launch_k1(d, s, st) : CRC32C_EINVAL;
     std::lock_guard<std::mutex> lk(d.mu);
     const bool timed = !(flags & CRC32C_ASYNC);
-    d.acquire(st);
-    if (timed) HIP_OK(hipEventRecord(d.ev0, st));
-    bool host_counted = false;
-    int rc = enqueue_device(d, s, st, timed, &host_counted);
-    if (rc) {
-        d.release(st);
-        return rc;
-    }
-    if (!timed) {
-        d.release(st);
-        return CRC32C_OK;
-    }
-    HIP_OK(hipEventRecord(d.ev1, st));
     // spans given by offsets / lengths are range-checked on the device
     unsigned long long nrange = 0;
     const bool checked = s.n && (s.offsets || s.lens);
-    if (checked && !host_counted) HIP_OK(hipMemcpyAsync(d.hbad, d.nbad, sizeof nrange, hipMemcpyDeviceToHost, st));
-    d.release(st);
+    {
+        Lease lease(d, st);  // (handed on before the host waits)
+        if (timed) HIP_OK(hipEventRecord(d.ev0, st));
+        bool host_counted = false;
+        const int rc = enqueue_device(d, s, st, timed, &host_counted);
+        if (rc || !timed) return rc;
+        HIP_OK(hipEventRecord(d.ev1, st));
+        if (checked && !host_counted) HIP_OK(hipMemcpyAsync(d.hbad, d.nbad, sizeof nrange, hipMemcpyDeviceToHost, st));
+    }
     HIP_OK(hipEventSynchronize(d.ev1));
     if (checked) {
         HIP_OK(hipStreamSynchronize(st));
@@ -1039,15 +1012,11 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
     }
     const bool dev = flags & CRC32C_DEVICE;
     if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
-    mcrc_dev::SpanArgs a{};
+    mcrc_dev::SpanArgs a = common_args(*d);
     a.base = (const uint8_t *)base;
     a.base_bytes = base_bytes;
     a.offsets = item_offsets;
-    a.nbad = d->nbad;
     a.n = n;
-    a.xpow = d->xpow;
-    a.tab8 = d->tab8;
-    a.zero = d->zero;
     a.region = region_bytes;
     a.cfl = (flags & CRC32C_CFLAGS64) ? 8u : 4u;
     Path path;
@@ -1060,15 +1029,13 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
         path.host_counted = path.small;
         // large batches: K5 or the planned path, routed on the device
         const bool k5 = !path.small && items_fused(a);
-        d->acquire(st);
-        if (!path.host_counted) (void)hipMemsetAsync(d->nbad, 0, sizeof(unsigned long long), st);
-        rc = k5 ? launch_items<MODE>(*d, a, st) : launch_units<MODE>(*d, a, st, path);
-        if (!rc && !path.host_counted)
-            rc = hipMemcpyAsync(d->hbad, d->nbad, sizeof(unsigned long long), hipMemcpyDeviceToHost, st) == hipSuccess
-                     ? CRC32C_OK
-                     : CRC32C_EHIP;
-        d->release(st);
-        if (rc) return rc;
+        {
+            Lease lease(*d, st);
+            if (!path.host_counted) (void)hipMemsetAsync(d->nbad, 0, sizeof(unsigned long long), st);
+            if ((rc = k5 ? launch_items<MODE>(*d, a, st) : launch_units<MODE>(*d, a, st, path))) return rc;
+            if (!path.host_counted)
+                HIP_OK(hipMemcpyAsync(d->hbad, d->nbad, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        }
         if ((flags & CRC32C_ASYNC) && !nbad) return CRC32C_OK;  // fire and forget
         HIP_OK(hipStreamSynchronize(st));
         if (nbad) *nbad = *d->hbad;
@@ -1076,41 +1043,34 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
     }
     hipStream_t st = d->stream;
     HIP_OK(hipSetDevice(d->id));
-    d->acquire(st);
-    struct Release {
-        Device *d;
-        hipStream_t st;
-        ~Release() {
-            (void)hipStreamSynchronize(st);
-            d->release(st);
-        }
-    } release_on_exit{d, st};
-    void *h_offs, *v_offs, *h_ok, *v_ok, *h_crc = nullptr, *v_crc = nullptr;
-    if (!d->grow_pinned(kPinOffs, n * 8, &h_offs, &v_offs) || !d->grow_pinned(kPinOk, n, &h_ok, &v_ok))
-        return CRC32C_ENOMEM;
+    Lease lease(*d, st, true);  // (every exit drains st first: the kernels write pinned scratch)
+    uint64_t *const h_offs = d->pin_offs.reserve(n * 8);
+    uint8_t *const h_ok = d->pin_ok.reserve(n);
+    if (!h_offs || !h_ok) return CRC32C_ENOMEM;
     memcpy(h_offs, item_offsets, n * 8);
     const uint8_t *mapped = device_view_range(base, base_bytes);
     // stamp results come back as CRCs (scattered into the caller's images
     // here) unless the kernel stamps the caller's page-locked buffer itself
     const bool crcs_back = MODE == 2 && !(path.small && mapped);
-    if (crcs_back && !d->grow_pinned(kPinCrc, n * 4, &h_crc, &v_crc)) return CRC32C_ENOMEM;
-    a.ok = (uint8_t *)v_ok;
-    a.out = (uint32_t *)v_crc;
+    const uint32_t *const h_crc = crcs_back ? d->pin_crc.reserve(n * 4) : nullptr;
+    if (crcs_back && !h_crc) return CRC32C_ENOMEM;
+    a.ok = d->pin_ok.dev();
+    a.out = crcs_back ? d->pin_crc.dev() : nullptr;
     if (path.small) {
         if (!mapped) {  // a pinned copy the kernel reads
-            void *h_stage, *v_stage;
-            if (!d->grow_pinned(kPinStage, base_bytes, &h_stage, &v_stage)) return CRC32C_ENOMEM;
+            uint8_t *const h_stage = d->pin_stage.reserve(base_bytes);
+            if (!h_stage) return CRC32C_ENOMEM;
             memcpy(h_stage, base, base_bytes);
-            mapped = (const uint8_t *)v_stage;
+            mapped = d->pin_stage.dev();
         }
         a.base = mapped;
-        a.offsets = (const uint64_t *)v_offs;
+        a.offsets = d->pin_offs.dev();
         path.host_counted = true;
         if ((rc = launch_units<MODE>(*d, a, st, path))) return rc;
     } else {
-        uint8_t *b = (uint8_t *)d->grow(kScrStage, base_bytes);
-        uint64_t *o = (uint64_t *)d->grow(kScrItemOffs, n * 8);
-        uint8_t *r = (uint8_t *)d->grow(kScrItemOut, n * 5 + 4);  // ok[n], then (4-B aligned) crc[n]
+        uint8_t *b = d->stage.reserve(base_bytes);
+        uint64_t *o = d->item_offs.reserve(n * 8);
+        uint8_t *r = d->item_out.reserve(n * 5 + 4);  // ok[n], then (4-B aligned) crc[n]
         if (!b || !o || !r) return CRC32C_ENOMEM;
         HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(o, h_offs, n * 8, hipMemcpyHostToDevice, st));
@@ -1121,18 +1081,16 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
         HIP_OK(hipMemsetAsync(d->nbad, 0, sizeof(unsigned long long), st));
         if ((rc = launch_units<MODE>(*d, a, st, path))) return rc;
         HIP_OK(hipMemcpyAsync(h_ok, a.ok, n, hipMemcpyDeviceToHost, st));
-        if (crcs_back) HIP_OK(hipMemcpyAsync(h_crc, a.out, n * 4, hipMemcpyDeviceToHost, st));
+        if (crcs_back) HIP_OK(hipMemcpyAsync(d->pin_crc.get(), a.out, n * 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(d->hbad, d->nbad, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));
-    const uint8_t *oks = (const uint8_t *)h_ok;
     if (crcs_back) {
         uint8_t *bb = (uint8_t *)base;
-        const uint32_t *crcs = (const uint32_t *)h_crc;
         for (uint64_t i = 0; i < n; ++i)
-            if (oks[i]) memcpy(bb + item_offsets[i] + 28, &crcs[i], 4);  // exptime (storage.c:567)
+            if (h_ok[i]) memcpy(bb + item_offsets[i] + 28, &h_crc[i], 4);  // exptime (storage.c:567)
     }
-    if (ok) memcpy(ok, oks, n);
+    if (ok) memcpy(ok, h_ok, n);
     if (nbad) *nbad = *d->hbad;
     return CRC32C_OK;
 }
@@ -1179,9 +1137,8 @@ struct Queue {
     // when it started) is queued behind it on the stream.  Each slot has
     // pinned, mapped descriptors for kSmallMax spans and its event.
     struct Slot {
-        uint64_t *addr = nullptr;
-        uint32_t *len = nullptr, *cin = nullptr, *out = nullptr;
-        void *v_addr = nullptr, *v_len = nullptr, *v_cin = nullptr, *v_out = nullptr;
+        MapBuf<uint64_t> addr;
+        MapBuf<uint32_t> len, cin, out;
         hipEvent_t done = nullptr;
         std::vector<crc32c_job *> jobs;  // empty: the slot is free
     } slot[2];
@@ -1194,14 +1151,8 @@ struct Queue {
         HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         const uint64_t n = mcrc_dev::kSmallMax;
         for (Slot &l : slot) {
-            HIP_OK(hipHostMalloc((void **)&l.addr, n * 8, hipHostMallocDefault));
-            HIP_OK(hipHostMalloc((void **)&l.len, n * 4, hipHostMallocDefault));
-            HIP_OK(hipHostMalloc((void **)&l.cin, n * 4, hipHostMallocDefault));
-            HIP_OK(hipHostMalloc((void **)&l.out, n * 4, hipHostMallocDefault));
-            HIP_OK(hipHostGetDevicePointer(&l.v_addr, l.addr, 0));
-            HIP_OK(hipHostGetDevicePointer(&l.v_len, l.len, 0));
-            HIP_OK(hipHostGetDevicePointer(&l.v_cin, l.cin, 0));
-            HIP_OK(hipHostGetDevicePointer(&l.v_out, l.out, 0));
+            if (!l.addr.reserve(n * 8) || !l.len.reserve(n * 4) || !l.cin.reserve(n * 4) || !l.out.reserve(n * 4))
+                return CRC32C_ENOMEM;
             HIP_OK(hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
         }
         HIP_OK(hipMalloc(&dnbad, sizeof(unsigned long long)));
@@ -1266,27 +1217,24 @@ struct Queue {
     // (enqueued, not waited for).
     int launch(Slot &l) {
         uint64_t k = 0;
+        uint64_t *const addr = l.addr.get();
+        uint32_t *const len = l.len.get(), *const cin = l.cin.get();
         for (crc32c_job *j : l.jobs) {
             const crc32c_spans &s = j->s;
             for (uint64_t i = 0; i < s.n; ++i, ++k) {
-                l.addr[k] = (uint64_t)(uintptr_t)(j->dbase + span_off(s, i));
-                l.len[k] = (uint32_t)span_len(s, i);
-                l.cin[k] = s.crc_in ? s.crc_in[i] : 0u;
+                addr[k] = (uint64_t)(uintptr_t)(j->dbase + span_off(s, i));
+                len[k] = (uint32_t)span_len(s, i);
+                cin[k] = s.crc_in ? s.crc_in[i] : 0u;
             }
         }
-        mcrc_dev::SpanArgs a{};
+        mcrc_dev::SpanArgs a = common_args(*d, dnbad);
         a.base = nullptr;  // spans at absolute addresses
         a.base_bytes = ~0ull;
-        a.offsets = (const uint64_t *)l.v_addr;
-        a.lens = (const uint32_t *)l.v_len;
-        a.crc_in = (const uint32_t *)l.v_cin;
-        a.out = (uint32_t *)l.v_out;
-        a.nbad = dnbad;
+        a.offsets = l.addr.dev();
+        a.lens = l.len.dev();
+        a.crc_in = l.cin.dev();
+        a.out = l.out.dev();
         a.n = k;
-        a.xpow = d->xpow;
-        a.tab8 = d->tab8;
-        a.zero = d->zero;
-        a.cfl = 4;
         int rc = launch_small<0>(*d, a, st);
         if (rc) return rc;
         HIP_OK(hipEventRecord(l.done, st));
@@ -1301,7 +1249,7 @@ struct Queue {
         if (!rc && hipEventSynchronize(l.done) != hipSuccess) rc = CRC32C_EHIP;
         uint64_t k = 0;
         for (crc32c_job *j : l.jobs) {
-            if (!rc) memcpy(j->s.out, l.out + k, j->s.n * 4);
+            if (!rc) memcpy(j->s.out, l.out.get() + k, j->s.n * 4);
             k += j->s.n;
             complete(j, rc);
         }
@@ -1618,12 +1566,7 @@ int crc32c_batch_chains(const crc32c_spans *iovs, const uint64_t *chain_first, u
     }
     std::lock_guard<std::mutex> lk(d->mu);
     hipStream_t st = dev ? (hipStream_t)stream : d->stream;
-    d->acquire(st);
-    struct Release {
-        Device *d;
-        hipStream_t st;
-        ~Release() { d->release(st); }
-    } release_on_exit{d, st};
+    Lease lease(*d, st);
     const uint32_t *crcs = iovs->out, *lens = iovs->lens;
     const uint64_t *first = chain_first;
     uint32_t *dout = out;
@@ -1639,7 +1582,7 @@ int crc32c_batch_chains(const crc32c_spans *iovs, const uint64_t *chain_first, u
         }
     } else {  // stage the fold's inputs (small: 4-8 B per iov / chain)
         const uint64_t n = iovs->n;
-        uint8_t *buf = (uint8_t *)d->grow(kScrStage, n * 8 + (nchains + 1) * 8 + nchains * 4 + 64);
+        uint8_t *buf = d->stage.reserve(n * 8 + (nchains + 1) * 8 + nchains * 4 + 64);
         if (!buf) return CRC32C_ENOMEM;
         uint32_t *c_d = (uint32_t *)buf, *l_d = lens ? c_d + n : nullptr;
         uint64_t *f_d = (uint64_t *)(buf + ((n * 8 + 7) & ~7ull));
@@ -1685,34 +1628,25 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
     if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
     std::lock_guard<std::mutex> lk(d->mu);
     const uint64_t nw = (base_bytes + wbuf_bytes - 1) / wbuf_bytes;
-    d->acquire(st);
-    struct Release {
-        Device *d;
-        hipStream_t st;
-        ~Release() { d->release(st); }
-    } release_on_exit{d, st};
+    Lease lease(*d, st);
     if (nw == 0 || nw >= 0x7fffffffull) {
         *nitems = *nbad = 0;
         return nw ? CRC32C_EINVAL : CRC32C_OK;
     }
     const uint8_t *dbase = (const uint8_t *)base;
     if (!dev) {
-        uint8_t *b = (uint8_t *)d->grow(kScrStage, base_bytes);
+        uint8_t *b = d->stage.reserve(base_bytes);
         if (!b) return CRC32C_ENOMEM;
         HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
         dbase = b;
     }
     // counts of nw wbufs and a zero: the exclusive scan's last entry is the total
-    uint32_t *cnt = (uint32_t *)d->grow(kScrWalkCnt, (nw + 1) * 4);
-    uint32_t *prefix = (uint32_t *)d->grow(kScrWalkPrefix, (nw + 2) * 4);
+    uint32_t *cnt = d->walk_cnt.reserve((nw + 1) * 4);
+    uint32_t *prefix = d->walk_prefix.reserve((nw + 2) * 4);
     if (!cnt || !prefix) return CRC32C_ENOMEM;
-    mcrc_dev::SpanArgs a{};
+    mcrc_dev::SpanArgs a = common_args(*d);
     a.base = dbase;
     a.base_bytes = base_bytes;
-    a.nbad = d->nbad;
-    a.xpow = d->xpow;
-    a.tab8 = d->tab8;
-    a.zero = d->zero;
     a.region = wbuf_bytes;
     a.cfl = (flags & CRC32C_CFLAGS64) ? 8u : 4u;
     // one walking wave per wbuf, kWalkWaves per workgroup
@@ -1727,7 +1661,7 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
     // whose slot buffer cannot be allocated.
     wo.kslot = (uint32_t)std::min<uint64_t>(wbuf_bytes / 2048, 8192);
     if (wo.kslot < 8) wo.kslot = 0;
-    wo.slots = wo.kslot ? (uint64_t *)d->grow(kScrWalkSlots, (size_t)nw * wo.kslot * 8) : nullptr;
+    wo.slots = wo.kslot ? d->walk_slots.reserve((size_t)nw * wo.kslot * 8) : nullptr;
     if (!wo.slots) wo.kslot = 0;
     HIP_OK(hipMemsetAsync(cnt + nw, 0, 4, st));
     hipLaunchKernelGGL(mcrc_dev::k_walk<false>, dim3(gw), bw, 0, st, a, nw, wo);
@@ -1741,8 +1675,8 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
         return CRC32C_OK;
     }
     const bool direct = dev && cap >= total;  // caller's device arrays take the results
-    uint64_t *doffs = direct ? offsets : (uint64_t *)d->grow(kScrWalkOffs, (size_t)total * 8);
-    uint8_t *dok = direct ? ok : (uint8_t *)d->grow(kScrWalkOk, total);
+    uint64_t *doffs = direct ? offsets : d->walk_offs.reserve((size_t)total * 8);
+    uint8_t *dok = direct ? ok : d->walk_ok.reserve(total);
     if (!doffs || !dok) return CRC32C_ENOMEM;
     a.offsets = doffs;
     a.ok = dok;
@@ -1761,14 +1695,14 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
     if (path.counted) {
         rc = ensure_plan(*d, total, plan_cap(a));
         if (rc) return rc;
-        a.span_acc = d->span_acc;
+        a.span_acc = d->span_acc.get();
     }
     wo.prefix = prefix;
     wo.offs = doffs;
     wo.err = d->nbad + 1;
-    wo.nunit = path.counted ? d->nunit : nullptr;
-    wo.irec = path.counted ? d->irec : nullptr;
-    wo.fast = path.counted ? d->fast : nullptr;
+    wo.nunit = path.counted ? d->nunit.get() : nullptr;
+    wo.irec = path.counted ? d->irec.get() : nullptr;
+    wo.fast = path.counted ? d->fast.get() : nullptr;
     HIP_OK(hipMemsetAsync(d->nbad, 0, 2 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(mcrc_dev::k_walk<true>, dim3(gw), bw, 0, st, a, nw, wo);
     rc = k5 ? launch_items<1>(*d, a, st) : launch_units<1>(*d, a, st, path);

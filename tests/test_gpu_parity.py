@@ -869,6 +869,116 @@ def test_concurrent_streams_share_plan_buffers(torch):
     assert not errors, errors
 
 
+_REGROW = {}
+
+
+def _regrow_data():
+    """The inputs and expected results of test_scratch_regrows_between_calls,
+    built once for both span paths and left unchanged."""
+    if _REGROW:
+        return _REGROW
+    rng = np.random.default_rng(1841)
+    # span batches: 64 spans of up to 40 000 B; 3 plan tiles and 5 spans of up to 2000 B
+    spans = []
+    for n, top in ((64, 40001), (3 * 2048 + 5, 2001)):
+        lens = rng.integers(0, top, n).astype(np.uint32)
+        offs = np.concatenate([[3], 3 + np.cumsum(lens[:-1].astype(np.uint64) + 1)]).astype(np.uint64)
+        host = rng.integers(0, 256, int(offs[-1] + lens[-1] + 16), dtype=np.uint8)
+        spans.append((host, offs, lens, oracle.batch(host, offs, lens)))
+    _REGROW["spans"] = spans
+    # item images: 4165 B (one block after the head fragment), about 1 % of other sizes
+    n, wbuf = 8200, 1 << 20
+    vlen = np.where(rng.random(n) < 0.01, rng.integers(0, 9000, n), 4096)
+    items = [layout.make_item(b"key%07d" % i, rng.integers(0, 256, int(vlen[i]), dtype=np.uint8).tobytes(), cas=i + 1)
+             for i in range(n)]
+    buf, offs = layout.pack_wbufs(items, wbuf)
+    soffs, slens = layout.spans_of(buf, offs)
+    assert (slens == 4133).sum() > 0.98 * n and (slens != 4133).sum() > 40
+    layout.store_crcs(buf, offs, oracle.batch(buf, soffs, slens))
+    # damaged before and after image 4096 and in the first 200: a flipped value
+    # bit (a stamp repairs it) or nbytes claiming a span past the wbuf (malformed)
+    flipped = np.array([5, 77, 1500, 4000, 4095, 4096, 6000, 8199])
+    malformed = np.array([11, 160, 2222, 4097, 7000])
+    other = np.flatnonzero(slens != 4133)
+    flipped = np.union1d(flipped, [other[1], other[-2]])  # (images the planned path takes, too)
+    assert not np.intersect1d(flipped, malformed).size
+    for v in flipped:
+        buf[int(soffs[v]) + 16 + int(rng.integers(0, slens[v] - 16))] ^= 1 << int(rng.integers(0, 8))
+    for v in malformed:
+        buf[int(offs[v]) + 32 + 2] ^= 0x10
+    stamped = buf.copy()  # what a stamp of every image leaves: the flipped images' CRCs over their bytes as they are
+    layout.store_crcs(stamped, offs[flipped], oracle.batch(buf, soffs[flipped], slens[flipped]))
+    _REGROW["items"] = (buf, offs, wbuf, flipped, malformed, stamped)
+    # pages of 64 KiB wbufs, a few items with a flipped bit
+    pwbuf = 64 << 10
+    pbuf, poffs = _mixed_page(rng, 3200, pwbuf, 3000)
+    assert pbuf.size >= 64 * pwbuf
+    pbuf, poffs = pbuf[:64 * pwbuf].copy(), poffs[poffs < 64 * pwbuf]
+    pbad = np.array([2, 100, int((poffs < 8 * pwbuf).sum()) - 1, 1000, poffs.size - 1])
+    for v in pbad:
+        pbuf[int(poffs[v]) + 48] ^= 0x04
+    _REGROW["pages"] = (pbuf, poffs, pwbuf, pbad)
+    return _REGROW
+
+
+def test_scratch_regrows_between_calls(torch):
+    """Every grow-only scratch buffer of the library regrown between calls of
+    one process on one stream, each result exact: span batches by device
+    offsets and lengths (64 long spans; 3 x 2048 + 5 short ones, past the
+    plan's tile size; the first again), device item images through the K5
+    routing and its fallback list (verify, stamp, verify at 4096 and at 8200
+    images: the second verify reports exactly the malformed ones), pageable
+    host images (9 MiB, 18 MiB, then under 1 MiB) and the device page walk
+    (8, then 64 wbufs of 64 KiB)."""
+    data = _regrow_data()
+    devs = [(_dev(torch, h), _dev(torch, o.view(np.int64)), _dev(torch, l.view(np.int32)), want)
+            for h, o, l, want in data["spans"]]
+    for k in (0, 1, 0):
+        d, do, dl, want = devs[k]
+        np.testing.assert_array_equal(_u32(mc.batch(d, offsets=do, lens=dl)), want)
+    buf, offs, wbuf, flipped, malformed, stamped = data["items"]
+    for n in (4096, 8200):
+        fl, mal = flipped[flipped < n], malformed[malformed < n]
+        want_ok = np.ones(n, np.uint8)
+        want_ok[mal] = 0
+        want_bad = want_ok.copy()
+        want_bad[fl] = 0
+        want_buf = buf.copy()
+        for v in fl:
+            o = int(offs[v])
+            want_buf[o + 28:o + 32] = stamped[o + 28:o + 32]
+        d, do = _dev(torch, buf), _dev(torch, offs[:n].view(np.int64))
+        ok, nbad = mc.verify_items(d, do, region_bytes=wbuf)
+        assert nbad == fl.size + mal.size
+        np.testing.assert_array_equal(ok.cpu().numpy(), want_bad)
+        ok, nbad = mc.stamp_items(d, do, region_bytes=wbuf)
+        assert nbad == mal.size
+        np.testing.assert_array_equal(ok.cpu().numpy(), want_ok)
+        np.testing.assert_array_equal(d.cpu().numpy(), want_buf)
+        ok, nbad = mc.verify_items(d, do, region_bytes=wbuf)
+        assert nbad == mal.size
+        np.testing.assert_array_equal(ok.cpu().numpy(), want_ok)
+    for size in (9 << 20, 18 << 20, 1 << 20):
+        n = int(np.searchsorted(offs, size)) - (size == 1 << 20)  # 9 and 18 MiB or just above; under 1 MiB
+        nbytes = int(offs[n])
+        assert (nbytes < size) == (size == 1 << 20) and abs(nbytes - size) < 9100
+        want_bad = np.ones(n, np.uint8)
+        want_bad[flipped[flipped < n]] = 0
+        want_bad[malformed[malformed < n]] = 0
+        ok, nbad = mc.verify_items(buf[:nbytes], offs[:n], region_bytes=wbuf)
+        assert nbad == n - int(want_bad.sum()) and nbad > 0
+        np.testing.assert_array_equal(ok, want_bad)
+    pbuf, poffs, pwbuf, pbad = data["pages"]
+    for nw in (8, 64):
+        want_offs = poffs[poffs < nw * pwbuf]
+        want_ok = np.ones(want_offs.size, np.uint8)
+        want_ok[pbad[pbad < want_offs.size]] = 0
+        got_offs, got_ok, nbad = mc.verify_pages(_dev(torch, pbuf[:nw * pwbuf]), pwbuf)
+        np.testing.assert_array_equal(got_offs.cpu().numpy().astype(np.uint64), want_offs)
+        np.testing.assert_array_equal(got_ok.cpu().numpy(), want_ok)
+        assert nbad == want_offs.size - int(want_ok.sum()) and nbad >= 3
+
+
 def test_realistic_item_spans_4133(torch):
     """config-1/config-5 geometry: 4133-byte spans at +32 of 4165-byte images."""
     items = [layout.make_item(b"key%07d" % i, np.random.default_rng(i).integers(0, 256, 4096, dtype=np.uint8).tobytes(),
