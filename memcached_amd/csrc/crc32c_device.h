@@ -61,6 +61,8 @@ struct LaneCtx {
     uint32_t lane4;    // (lane & 31) << 2
     uint32_t lane4hi;  // lane4 | 0x10000 (selects the second 64 KiB table set)
 };
+// (li: the lane's index in its 32-lane group)
+__device__ __forceinline__ LaneCtx make_lane_ctx(uint32_t li) { return {li << 2, (li << 2) | 0x10000u}; }
 
 template <int SLICE>
 struct Step;
@@ -169,6 +171,15 @@ __device__ __forceinline__ uint32_t group_reduce32_pair_span(uint32_t a, uint32_
     v = reduce_level<2>(v, (lane & 7u) < 2u);
     v = reduce_level<3>(v, (lane & 15u) < 2u);
     return reduce_level4_span(v, (lane & 31u) < 2u);
+}
+
+// One item per group whose level 0 is done (the odd last step of the four /
+// two / one step loops): levels 1 to 4 into lane 0.
+__device__ __forceinline__ uint32_t group_reduce32_single_span(uint32_t v, uint32_t lane) {
+    v = reduce_level<1>(v, (lane & 3u) == 0u);
+    v = reduce_level<2>(v, (lane & 7u) == 0u);
+    v = reduce_level<3>(v, (lane & 15u) == 0u);
+    return reduce_level4_span(v, (lane & 31u) == 0u);
 }
 
 __device__ __forceinline__ uint32_t group_reduce32_quad_span(uint32_t ab, uint32_t cd, uint32_t lane) {

@@ -1,6 +1,6 @@
 """Integer restatement of the span kernels' work-unit geometry and of the
-per-span correction (memcached_amd/csrc/crc32c_kernels.hip: nseg_of,
-span_head, span_units, make_unit, load_block, span_corr).  Test
+per-span correction (memcached_amd/csrc/: k_common.h nseg_of, span_head,
+span_corr; k_spans.h make_unit, load_block; k_plan.h span_units).  Test
 infrastructure: the CPU tests check the addressing and the algebra with it,
 without a GPU."""
 SEG = 128 * 1024  # kSegBytes
@@ -139,7 +139,7 @@ def xpow8_inv(t):
 
 
 def one_block(p, length):
-    """(is one block or none, none, G1) -- k_blocks' test (crc32c_kernels.hip one_block)."""
+    """(is one block or none, none, G1) -- k_blocks' test (k_common.h one_block)."""
     kh = p & 15
     vlen = length + tail_pad(p, length)
     x = vlen + kh
@@ -151,7 +151,7 @@ def one_block(p, length):
     return none or (drop and vlen - g1o == BLOCK), none, p + g1o
 
 
-# --- balanced plan (crc32c_kernels.hip span_blocks, unit_piece, put_unit) ---
+# --- balanced plan (k_plan.h span_blocks, put_unit; k_spans.h unit_piece) ---
 
 SEG_BLOCKS = SEG // BLOCK
 BALANCE_MIN_PER = 2  # kBalanceMinPer

@@ -1,5 +1,5 @@
-"""CPU restatement of K5's line-anchored form (round 4, crc32c_kernels.hip
-k_items, MCRC_K5_LINES): the block of an image starts and ends on 128-B lines,
+"""CPU restatement of K5's line-anchored form (round 4, k_lines.h
+k_lines): the block of an image starts and ends on 128-B lines,
 so no HBM line is read both by a block and by an image's per-lane prep.
 
 For span D = [p, E) with initial CRC c:

@@ -109,7 +109,7 @@ def test_no_64bit_shift_takes_its_amount_from_the_top_vgpr(tmp_path):
 
 
 def test_parse_hdr_has_no_64bit_shift(tmp_path):
-    """parse_hdr (crc32c_kernels.hip) funnels the header bytes with
+    """parse_hdr (k_common.h) funnels the header bytes with
     v_alignbyte_b32: a probe kernel holding only the parse, for both pointer
     types the library instantiates, has no 64-bit VALU shift."""
     hipcc = "/opt/rocm/bin/hipcc"

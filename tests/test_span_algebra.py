@@ -1,5 +1,5 @@
-"""CPU check of the span kernels' algebra (crc32c_kernels.hip "Pieces as they
-lie", span_corr, mask_tail, k_final): with R = the XOR over a span's work
+"""CPU check of the span kernels' algebra (k_common.h "Pieces as they
+lie", span_corr; k_spans.h mask_tail; k_plan.h k_final): with R = the XOR over a span's work
 units of M_{Ea - e}(raw of the unit's 16-B pieces as they lie in memory, the
 span's tail bytes [E, Ea) cleared) -- what k_spans accumulates -- and Z from
 the span's thread,

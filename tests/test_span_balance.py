@@ -1,5 +1,5 @@
-"""CPU check of the span kernel's balanced plan (crc32c_kernels.hip
-span_blocks, unit_piece, put_unit / k_expand, k_spans' group ranges),
+"""CPU check of the span kernel's balanced plan (k_plan.h span_blocks,
+put_unit / k_expand, k_spans.h unit_piece and k_spans' group ranges),
 restated in tests/span_model.py:
   * span_blocks (k_count's packed block count) is the sum of the units' niters;
   * group g's records [starts[g], starts[g + 1]) hold exactly the blocks

@@ -1,6 +1,6 @@
 """CPU check of the span kernel's work-unit geometry (restated in
-tests/span_model.py from crc32c_kernels.hip make_unit / span_units /
-load_block): for every unit, the 16-B pieces read from memory lie inside
+tests/span_model.py from k_spans.h make_unit / load_block and k_plan.h
+span_units): for every unit, the 16-B pieces read from memory lie inside
 [floor16(p), e) of the unit (so no load leaves the pages of the span), and the
 units of a span together with its head fragment (the bytes [p, G1) that the
 span's thread reads when span_head drops them) cover every byte of [p, E)

@@ -1,5 +1,5 @@
 """CPU check of the device page walk's round-trip algebra (k_walk in
-crc32c_kernels.hip, restated here): one wave per wbuf guesses that the next 64
+k_walk.h, restated here): one wave per wbuf guesses that the next 64
 items all have the last item's size, reads their headers in one round trip,
 and keeps the guesses up to the first lane whose item breaks the run.  The
 claim to check is that this gives exactly the sequential walk of
