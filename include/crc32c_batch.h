@@ -14,6 +14,11 @@
  *                          (storage.c:163-170).
  *   crc32c_verify_pages    the same over whole pages, walked on the device as
  *                          storage_compact_readback walks them.
+ *   crc32c_stamp_pages     crc32c_stamp_items over a wbuf walked on the device
+ *                          the same way: no offset list; with
+ *                          CRC32C_KEEP_STAMPED the images compaction copied with
+ *                          their CRC (storage.c:1004-1006) are verified, not
+ *                          stamped again.
  *   crc32c_verify_items    the read-verify compare of storage.c:159-178 applied
  *                          to every item image of a packed extstore page
  *                          (walk of storage.c:950-960): CRC over
@@ -51,7 +56,7 @@ extern "C" {
 #define CRC32C_ENOMEM (-4) /* device or pinned allocation failed */
 #define CRC32C_ERANGE (-5) /* a span lies outside [base, base + base_bytes): it was
                               not read and its out[] entry is 0 */
-#define CRC32C_EWALK (-6)  /* crc32c_verify_pages: the device walk's count and emit
+#define CRC32C_EWALK (-6)  /* crc32c_verify_pages / _stamp_pages: the device walk's count and emit
                               passes disagreed on some wbuf (an internal invariant;
                               the results are not valid) */
 
@@ -66,6 +71,15 @@ extern "C" {
                                  --enable-large-client-flags (configure.ac:139-140):
                                  client_flags_t is 8 bytes, so ITEM_CFLAGS adds 8 to
                                  ITEM_ntotal instead of 4 (memcached.h:96-100, :149-152) */
+#define CRC32C_KEEP_STAMPED 0x10u /* stamp calls: an image whose exptime is not 0 already
+                                 carries its CRC (compaction copies images with it,
+                                 storage.c:1004-1006): it is verified against that
+                                 value and not written; see crc32c_stamp_items */
+
+/* ok[] values of the stamp calls (0: malformed, or a carried image whose stored
+ * CRC does not match) */
+#define CRC32C_ITEM_STAMPED 1 /* the CRC was written into exptime */
+#define CRC32C_ITEM_KEPT 2    /* CRC32C_KEEP_STAMPED: the stored CRC matched, nothing written */
 
 /* Longest span: 2 GiB - 64 KiB, twice the largest item memcached stores
  * (ITEM_SIZE_MAX_UPPER_LIMIT, memcached.h:115).  A device span past it is not
@@ -163,10 +177,46 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
  * malformed images are left untouched and counted in *nbad.  region_bytes as
  * for crc32c_verify_items.  Images are expected not to overlap (extstore
  * packs them back to back); where one image's span covers another's exptime,
- * its CRC may or may not include that image's new stamp. */
+ * its CRC may or may not include that image's new stamp.
+ *
+ * With CRC32C_KEEP_STAMPED a wbuf may mix fresh images with images carried over
+ * verbatim with their stored CRC (compaction, storage.c:1004-1006).  Per image
+ * whose header is sane, c = crc32c(0, image + 32, ITEM_ntotal - 32):
+ *   exptime == 0 (fresh: the writer leaves it 0): c is written into exptime,
+ *                ok[i] = CRC32C_ITEM_STAMPED;
+ *   exptime != 0 (carried): nothing is written; ok[i] = CRC32C_ITEM_KEPT when
+ *                exptime == c, else ok[i] = 0 and the image counts in *nbad
+ *                (count it like badcrc_from_extstore: the image was damaged
+ *                before it was copied).
+ * Malformed images are untouched, ok[i] = 0, counted, as without the flag.  A
+ * carried image whose stored CRC is genuinely 0 is taken for fresh: intact, it
+ * is re-stamped with the same 0; corrupt, its damage is covered by a new CRC
+ * (probability 2^-32 per corrupt image).  Without the flag nothing changes:
+ * every sane image is stamped. */
 int crc32c_stamp_items(void *base, uint64_t base_bytes, uint64_t region_bytes,
                        const uint64_t *item_offsets, uint64_t n, uint8_t *ok, uint64_t *nbad,
                        unsigned flags, void *stream);
+
+/* crc32c_stamp_items with the walk done on the device: [base, base_bytes) is
+ * walked exactly as crc32c_verify_pages walks it (wbuf_bytes pieces, items
+ * packed from each piece's start, nkey == 0 or fewer than 48 bytes left end
+ * it; CRC32C_EWALK as there) and every image found is stamped, or with
+ * CRC32C_KEEP_STAMPED stamped or verified, as crc32c_stamp_items does with
+ * region_bytes = wbuf_bytes.  Host or device per flags; the call returns when
+ * the stamps are written (the walk's count is read back, so CRC32C_ASYNC has no
+ * effect).  *nitems = images found and *nbad = bad ones, always filled; the
+ * first min(cap, *nitems) offsets and ok flags (CRC32C_ITEM_*) are written, in
+ * walk order, when cap > 0.  Unlike crc32c_verify_pages' count-only query,
+ * cap == 0 still stamps every image: offsets / ok may then be NULL (a caller
+ * that wants no per-item output, e.g. extstore's _submit_wbuf).  Images behind
+ * a header that stops a piece's walk are neither stamped nor counted.  A wbuf
+ * that is still open, its tail not yet zeroed, is passed with base_bytes = the
+ * bytes used, so the walk never reads what lies behind them (INTEGRATION.md
+ * section 2: the hook runs before the tail memset).  Scratch as for
+ * crc32c_verify_pages. */
+int crc32c_stamp_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets,
+                       uint8_t *ok, uint64_t cap, uint64_t *nitems, uint64_t *nbad, unsigned flags,
+                       void *stream);
 
 /* Asynchronous form of crc32c_batch: returns at once with a job handle;
  * crc32c_batch_wait blocks until out[] is filled and frees the handle.

@@ -8,6 +8,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``batch``        out[i] = crc32c(crc_in[i] or 0, span i)  (storage.c:567, :172)
 * ``verify_items`` stored-CRC check of packed item images (storage.c:160-178)
 * ``stamp_items``  spill CRC written into each image's exptime (storage.c:567)
+* ``stamp_pages``  walk + stamp whole wbufs on the device (no offset list)
 * ``verify_pages`` walk + verify whole pages on the device (storage.c:950-1070)
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
@@ -18,13 +19,15 @@ HIP device, enqueued on torch's current stream.
 from __future__ import annotations
 
 import ctypes
+import operator
 
 import numpy as np
 
 from . import _lib
-from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, Crc32cError, check, lib
+from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
-__all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "verify_pages", "batch_chains", "batch_multi",
+__all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
+           "batch_multi",
            "shard_cuts", "queue_stats", "set_small_max", "gpu_count", "Crc32cError"]
 
 
@@ -179,13 +182,18 @@ def verify_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False)
     return ok, int(nbad.value)
 
 
-def stamp_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False):
+def stamp_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False, keep_stamped=False):
     """Write the spill CRC of every item image into its exptime field, in place
     (storage.c:567 for a whole wbuf at once).  Returns (ok, nbad): ok marks
-    stamped images, nbad counts malformed ones (left untouched)."""
+    stamped images (1), nbad counts malformed ones (left untouched).
+
+    ``keep_stamped`` (CRC32C_KEEP_STAMPED): an image whose exptime is not 0
+    carries its CRC already (compaction copies images with it); it is verified
+    against that value and never written: ok = 2 when it matches, else 0 and
+    counted in nbad."""
     dev = _is_torch(buf) and buf.is_cuda
     nbad = ctypes.c_uint64(0)
-    fl = CRC32C_CFLAGS64 if cflags64 else 0
+    fl = (CRC32C_CFLAGS64 if cflags64 else 0) | (CRC32C_KEEP_STAMPED if keep_stamped else 0)
     if dev:
         import torch
         n = item_offsets.numel()
@@ -206,6 +214,53 @@ def stamp_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False):
                                     ok.ctypes.data, ctypes.byref(nbad), fl, None)
     check(rc, "crc32c_stamp_items")
     return ok, int(nbad.value)
+
+
+def stamp_pages(buf, wbuf_bytes, keep_stamped=False, stream=None, cflags64=False):
+    """Walk every wbuf-sized piece of ``buf`` on the device, as verify_pages
+    does, and stamp each item image found, in place (``keep_stamped`` as for
+    stamp_items).  Returns (item offsets, ok flags, nbad) in walk order.
+
+    An open wbuf whose tail is not zeroed yet is passed as a slice of the
+    bytes used.  Device buffers are walked once more beforehand (a count-only
+    crc32c_verify_pages query) to size the result tensors exactly."""
+    try:
+        wbuf_bytes = operator.index(wbuf_bytes)
+    except TypeError:
+        wbuf_bytes = 0
+    if wbuf_bytes <= 0:
+        raise ValueError("wbuf_bytes: need a positive integer")
+    dev = _is_torch(buf) and buf.is_cuda
+    nitems, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    fl = (CRC32C_CFLAGS64 if cflags64 else 0) | (CRC32C_KEEP_STAMPED if keep_stamped else 0)
+    if dev:
+        import torch
+        if not buf.is_contiguous():
+            raise ValueError("buf: need a contiguous device tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(buf.device).cuda_stream
+        nbytes = buf.numel() * buf.element_size()
+        check(lib.crc32c_verify_pages(buf.data_ptr(), nbytes, wbuf_bytes, None, None, 0, ctypes.byref(nitems),
+                                      ctypes.byref(nbad), CRC32C_DEVICE | fl, stream), "crc32c_verify_pages")
+        cap = nitems.value
+        offs = torch.empty(cap, dtype=torch.int64, device=buf.device)
+        ok = torch.empty(cap, dtype=torch.uint8, device=buf.device)
+        check(lib.crc32c_stamp_pages(buf.data_ptr(), nbytes, wbuf_bytes, offs.data_ptr(), ok.data_ptr(), cap,
+                                     ctypes.byref(nitems), ctypes.byref(nbad), CRC32C_DEVICE | fl, stream),
+              "crc32c_stamp_pages")
+    else:
+        if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8 and buf.flags.writeable
+                and buf.flags.c_contiguous):
+            raise TypeError("stamp_pages needs a writable contiguous uint8 numpy array (stamped in place)")
+        # an image is >= 50 bytes and each wbuf's last counted image may run past its end
+        cap = buf.size // 50 + -(-buf.size // wbuf_bytes)
+        offs = np.empty(cap, np.uint64)
+        ok = np.empty(cap, np.uint8)
+        check(lib.crc32c_stamp_pages(buf.ctypes.data, buf.size, wbuf_bytes, offs.ctypes.data, ok.ctypes.data, cap,
+                                     ctypes.byref(nitems), ctypes.byref(nbad), fl, None), "crc32c_stamp_pages")
+    n = nitems.value
+    assert n <= cap, "item count above the proven bound"
+    return offs[:n], ok[:n], int(nbad.value)
 
 
 def verify_pages(buf, wbuf_bytes, stream=None, cflags64=False):

@@ -12,7 +12,9 @@
 //     headers): k_final<MODE 1> checks the CRC stored in the item's exptime
 //     field (storage.c:160-178 over the page walk of storage.c:950-960);
 //     k_final<MODE 2> stamps it (the spill CRC of storage.c:567, batched per
-//     wbuf).  k_walk walks the pages on the device.
+//     wbuf); k_final<MODE 3> (CRC32C_KEEP_STAMPED) stamps the images whose
+//     exptime is 0 and checks the others.  k_walk walks the pages on the
+//     device.
 // K4  k_blocks: spans whose unit is one 4 KiB block (K1's loop, gathered).
 // K5  k_lines<MODE>: spans or item images whose span is one 4 KiB window of
 //     whole lines after a short head (every 4165-B image of config 5 and the

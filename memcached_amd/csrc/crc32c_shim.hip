@@ -315,6 +315,7 @@ int init_device(Device &d, int id) {
         (const void *)mcrc_dev::k_small<0>,
         (const void *)mcrc_dev::k_small<1>,
         (const void *)mcrc_dev::k_small<2>,
+        (const void *)mcrc_dev::k_small<3>,
         (const void *)mcrc_dev::k_blocks<false, true>,
         (const void *)mcrc_dev::k_blocks<true, true>,
         (const void *)mcrc_dev::k_blocks<true, false>,
@@ -322,6 +323,7 @@ int init_device(Device &d, int id) {
         (const void *)mcrc_dev::k_lines<0, false>,
         (const void *)mcrc_dev::k_lines<1, true>,
         (const void *)mcrc_dev::k_lines<2, true>,
+        (const void *)mcrc_dev::k_lines<3, true>,
     };
     for (const void *k : k160)
         HIP_OK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mcrc_dev::kLdsImageK1Bytes));
@@ -613,7 +615,8 @@ int launch_units(Device &d, mcrc_dev::SpanArgs a, hipStream_t st, Path path) {
     return CRC32C_OK;
 }
 
-// K5 over the item images of a (MODE 1 verify, MODE 2 stamp; device memory,
+// K5 over the item images of a (MODE 1 verify, MODE 2 stamp, MODE 3 stamp that
+// keeps carried CRCs; device memory,
 // a.nbad zeroed by the caller): k_census routes the batch on the device,
 // k_lines checksums the one-block images (+ k_fix for stamps) and lists the
 // others, and the planned path takes that list with its length read on the
@@ -626,10 +629,11 @@ int launch_items(Device &d, mcrc_dev::SpanArgs a, hipStream_t st) {
     io.fb = d.fb.reserve(n * 4);
     io.nfb = d.nfb;
     io.route = d.route;
-    if (MODE == 2) io.rt = d.rt.reserve(n * 8);
+    constexpr bool kStamp = MODE >= 2;
+    if (kStamp) io.rt = d.rt.reserve(n * 8);
     uint64_t *fo = d.fb_offs.reserve(n * 8);
     uint8_t *fok = d.fb_ok.reserve(n);
-    if (!io.fb || (MODE == 2 && !io.rt) || !fo || !fok) return CRC32C_ENOMEM;
+    if (!io.fb || (kStamp && !io.rt) || !fo || !fok) return CRC32C_ENOMEM;
     HIP_OK(hipMemsetAsync(d.nfb, 0, 4, st));
     hipLaunchKernelGGL(mcrc_dev::k_census<MODE>, dim3(1), dim3(mcrc_dev::kCensus), 0, st, a, d.route);
     launch_k5<MODE, true>(d, a, io, st);
@@ -645,7 +649,7 @@ int launch_items(Device &d, mcrc_dev::SpanArgs a, hipStream_t st) {
             if (armed) (void)hipStreamWaitEvent(st, ev, 0);
         }
     } join{st, d.join};
-    if (MODE == 2) {
+    if (kStamp) {
         // k_fix (the stamps of the images k_lines checksummed) on the side
         // stream, beside the planned path of the images it listed: its
         // scattered partial-sector writes and that path's small launches
@@ -668,7 +672,7 @@ int launch_items(Device &d, mcrc_dev::SpanArgs a, hipStream_t st) {
     f.dn = d.nfb;  // (f.n = n: the list's upper bound)
     f.ok = want_ok ? fok : nullptr;
     int rc = launch_units<MODE>(d, f, st, Path{});
-    if (MODE == 2) {
+    if (kStamp) {
         join.armed = false;
         HIP_OK(hipStreamWaitEvent(st, d.join, 0));  // (also when the planned path failed)
     }
@@ -990,7 +994,8 @@ int device_batch(Device &d, const crc32c_spans &s, unsigned flags, hipStream_t s
     return nrange ? CRC32C_ERANGE : CRC32C_OK;
 }
 
-// Item-image batches (verify: MODE 1, stamp: MODE 2) over a packed buffer of
+// Item-image batches (verify: MODE 1, stamp: MODE 2, stamp with
+// CRC32C_KEEP_STAMPED: MODE 3) over a packed buffer of
 // item images at item_offsets.
 //   device: in place on the caller's stream;
 //   host, small (at most 8 MiB, a wbuf or an IO batch): one k_small launch on
@@ -1051,7 +1056,7 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
     const uint8_t *mapped = device_view_range(base, base_bytes);
     // stamp results come back as CRCs (scattered into the caller's images
     // here) unless the kernel stamps the caller's page-locked buffer itself
-    const bool crcs_back = MODE == 2 && !(path.small && mapped);
+    const bool crcs_back = MODE >= 2 && !(path.small && mapped);
     const uint32_t *const h_crc = crcs_back ? d->pin_crc.reserve(n * 4) : nullptr;
     if (crcs_back && !h_crc) return CRC32C_ENOMEM;
     a.ok = d->pin_ok.dev();
@@ -1088,7 +1093,7 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
     if (crcs_back) {
         uint8_t *bb = (uint8_t *)base;
         for (uint64_t i = 0; i < n; ++i)
-            if (h_ok[i]) memcpy(bb + item_offsets[i] + 28, &h_crc[i], 4);  // exptime (storage.c:567)
+            if (h_ok[i] == CRC32C_ITEM_STAMPED) memcpy(bb + item_offsets[i] + 28, &h_crc[i], 4);  // exptime (storage.c:567)
     }
     if (ok) memcpy(ok, h_ok, n);
     if (nbad) *nbad = *d->hbad;
@@ -1438,6 +1443,163 @@ MultiWorker *multi_worker(int index) {
 }  // namespace
 
 // ---------------------------------------------------------------------------
+// The page walk (crc32c_verify_pages / crc32c_stamp_pages)
+// ---------------------------------------------------------------------------
+namespace {
+
+// The device walk shared by crc32c_verify_pages and crc32c_stamp_pages: the
+// count pass (walk_count: k_walk<false>, the scan, the total read back) and the
+// emit pass (walk_emit: k_walk<true> writes the items' offsets on the device).
+struct PageWalk {
+    mcrc_dev::SpanArgs a;  // base (the device's copy of a host buffer), base_bytes, region, cfl;
+                           // after walk_emit also offsets and n (the caller sets ok / out)
+    mcrc_dev::WalkOut wo;
+    uint64_t nw = 0;       // wbufs
+    int gw = 0;            // k_walk's grid
+    uint32_t total = 0;    // items found
+    Path path;             // how the items run (walk_emit)
+    bool k5 = false;
+};
+
+int walk_count(Device &d, hipStream_t st, const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t nw,
+               unsigned flags, PageWalk *w) {
+    const uint8_t *dbase = (const uint8_t *)base;
+    if (!(flags & CRC32C_DEVICE)) {
+        uint8_t *b = d.stage.reserve(base_bytes);
+        if (!b) return CRC32C_ENOMEM;
+        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
+        dbase = b;
+    }
+    // counts of nw wbufs and a zero: the exclusive scan's last entry is the total
+    uint32_t *cnt = d.walk_cnt.reserve((nw + 1) * 4);
+    uint32_t *prefix = d.walk_prefix.reserve((nw + 2) * 4);
+    if (!cnt || !prefix) return CRC32C_ENOMEM;
+    mcrc_dev::SpanArgs &a = w->a;
+    a = common_args(d);
+    a.base = dbase;
+    a.base_bytes = base_bytes;
+    a.region = wbuf_bytes;
+    a.cfl = (flags & CRC32C_CFLAGS64) ? 8u : 4u;
+    // one walking wave per wbuf, kWalkWaves per workgroup
+    w->nw = nw;
+    w->gw = (int)std::min<uint64_t>((nw + mcrc_dev::kWalkWaves - 1) / mcrc_dev::kWalkWaves, 65535);
+    const dim3 bw(64 * mcrc_dev::kWalkWaves);
+    mcrc_dev::WalkOut &wo = w->wo;
+    wo = mcrc_dev::WalkOut{};
+    wo.cnt = cnt;
+    wo.prefix = prefix;
+    // the count pass keeps each wbuf's first offsets (one per 2 KiB of wbuf:
+    // every 4 MiB wbuf of items of at least 2 KiB; 8 B per 2 KiB, 0.4 % of the
+    // walked bytes), so a K5 verify's emit pass copies them instead of walking
+    // again.  Wbufs under 16 KiB keep none (walked twice), and so does a walk
+    // whose slot buffer cannot be allocated.
+    wo.kslot = (uint32_t)std::min<uint64_t>(wbuf_bytes / 2048, 8192);
+    if (wo.kslot < 8) wo.kslot = 0;
+    wo.slots = wo.kslot ? d.walk_slots.reserve((size_t)nw * wo.kslot * 8) : nullptr;
+    if (!wo.slots) wo.kslot = 0;
+    HIP_OK(hipMemsetAsync(cnt + nw, 0, 4, st));
+    hipLaunchKernelGGL(mcrc_dev::k_walk<false>, dim3(w->gw), bw, 0, st, a, nw, wo);
+    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw + 1, prefix);
+    HIP_OK(hipMemcpyAsync(&w->total, prefix + nw, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return CRC32C_OK;
+}
+
+// The emit pass writes the offsets into doffs (device memory, w->total
+// entries): copied from the count pass's slots, or for a wbuf of more items
+// than those (or with no slots kept) by walking it again.  A planned verify
+// then reads the headers in k_count, in parallel (round 6; the emit pass used
+// to walk again and write k_count's entries itself, one header per round trip
+// on mixed pages); only when no slots are kept does the second walk write a
+// verify's entries too (the headers are then read once more, not twice; a
+// stamp's entries are always k_count's).  Zeroes d.nbad[0..1]; the walk's
+// self-check counts into d.nbad[1].
+int walk_emit(Device &d, hipStream_t st, PageWalk *w, uint64_t *doffs, bool verify) {
+    mcrc_dev::SpanArgs &a = w->a;
+    mcrc_dev::WalkOut &wo = w->wo;
+    a.offsets = doffs;
+    a.n = w->total;
+    Path &path = w->path;
+    path = Path{};
+    path.small = takes_small<1>(a);
+    w->k5 = !path.small && items_fused(a);  // (then the walk writes offsets only)
+    path.counted = verify && !path.small && !w->k5 && wo.kslot == 0;
+    if (path.counted) {
+        const int rc = ensure_plan(d, w->total, plan_cap(a));
+        if (rc) return rc;
+        a.span_acc = d.span_acc.get();
+    }
+    wo.offs = doffs;
+    wo.err = d.nbad + 1;
+    wo.nunit = path.counted ? d.nunit.get() : nullptr;
+    wo.irec = path.counted ? d.irec.get() : nullptr;
+    wo.fast = path.counted ? d.fast.get() : nullptr;
+    HIP_OK(hipMemsetAsync(d.nbad, 0, 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(mcrc_dev::k_walk<true>, dim3(w->gw), dim3(64 * mcrc_dev::kWalkWaves), 0, st, a, w->nw, wo);
+    HIP_OK(hipGetLastError());
+    return CRC32C_OK;
+}
+
+// crc32c_stamp_pages after the count pass found w.total > 0 images.
+//   device: the images are stamped in place (K5 or the planned path, routed
+//     as crc32c_stamp_items routes them);
+//   host: the kernels run on the staged copy and write CRCs and ok flags
+//     beside it; offsets, flags and CRCs come back through pinned scratch and
+//     the stamps are scattered into the caller's buffer here.
+template <int MODE>
+int stamp_walked(Device &d, hipStream_t st, PageWalk &w, void *base, bool dev, uint64_t *offsets, uint8_t *ok,
+                 uint64_t cap, uint64_t *nbad) {
+    const uint64_t total = w.total, k = std::min<uint64_t>(cap, total);
+    const bool direct = dev && cap >= total;  // caller's device arrays take the results
+    uint64_t *doffs = direct ? offsets : d.walk_offs.reserve((size_t)total * 8);
+    // (a device call that wants no per-item output computes no ok flags)
+    uint8_t *dok = direct ? ok : (!dev || cap) ? d.walk_ok.reserve(total) : nullptr;
+    if (!doffs || (!dok && (!dev || cap))) return CRC32C_ENOMEM;
+    uint64_t *h_offs = nullptr;
+    uint8_t *h_ok = nullptr;
+    uint32_t *h_crc = nullptr, *dcrc = nullptr;
+    if (!dev) {
+        dcrc = (uint32_t *)d.item_out.reserve((size_t)total * 4);
+        h_offs = d.pin_offs.reserve(total * 8);
+        h_ok = d.pin_ok.reserve(total);
+        h_crc = d.pin_crc.reserve(total * 4);
+        if (!dcrc || !h_offs || !h_ok || !h_crc) return CRC32C_ENOMEM;
+    }
+    w.a.ok = dok;
+    w.a.out = dcrc;  // device: nullptr, stamp the images
+    int rc = walk_emit(d, st, &w, doffs, false);
+    if (rc) return rc;
+    // (K5's k_fix stamps the images themselves: staged images take the planned path)
+    rc = dev && w.k5 ? launch_items<MODE>(d, w.a, st) : launch_units<MODE>(d, w.a, st, w.path);
+    if (rc) return rc;
+    HIP_OK(hipMemcpyAsync(d.hbad, d.nbad, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (dev && !direct && k) {
+        HIP_OK(hipMemcpyAsync(offsets, doffs, k * 8, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(ok, dok, k, hipMemcpyDeviceToDevice, st));
+    }
+    if (!dev) {
+        HIP_OK(hipMemcpyAsync(h_offs, doffs, total * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ok, dok, total, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_crc, dcrc, total * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    *nbad = d.hbad[0];
+    if (d.hbad[1]) return CRC32C_EWALK;
+    if (!dev) {
+        uint8_t *bb = (uint8_t *)base;
+        for (uint64_t i = 0; i < total; ++i)
+            if (h_ok[i] == CRC32C_ITEM_STAMPED) memcpy(bb + h_offs[i] + 28, &h_crc[i], 4);  // exptime (storage.c:567)
+        if (k) {
+            memcpy(offsets, h_offs, k * 8);
+            memcpy(ok, h_ok, k);
+        }
+    }
+    return CRC32C_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
 // Batch C ABI
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -1614,6 +1776,8 @@ int crc32c_verify_items(const void *base, uint64_t base_bytes, uint64_t region_b
 
 int crc32c_stamp_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets,
                        uint64_t n, uint8_t *ok, uint64_t *nbad, unsigned flags, void *stream) {
+    if (flags & CRC32C_KEEP_STAMPED)
+        return item_images<3>(base, base_bytes, region_bytes, item_offsets, n, ok, nbad, flags, stream);
     return item_images<2>(base, base_bytes, region_bytes, item_offsets, n, ok, nbad, flags, stream);
 }
 
@@ -1633,42 +1797,9 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
         *nitems = *nbad = 0;
         return nw ? CRC32C_EINVAL : CRC32C_OK;
     }
-    const uint8_t *dbase = (const uint8_t *)base;
-    if (!dev) {
-        uint8_t *b = d->stage.reserve(base_bytes);
-        if (!b) return CRC32C_ENOMEM;
-        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
-        dbase = b;
-    }
-    // counts of nw wbufs and a zero: the exclusive scan's last entry is the total
-    uint32_t *cnt = d->walk_cnt.reserve((nw + 1) * 4);
-    uint32_t *prefix = d->walk_prefix.reserve((nw + 2) * 4);
-    if (!cnt || !prefix) return CRC32C_ENOMEM;
-    mcrc_dev::SpanArgs a = common_args(*d);
-    a.base = dbase;
-    a.base_bytes = base_bytes;
-    a.region = wbuf_bytes;
-    a.cfl = (flags & CRC32C_CFLAGS64) ? 8u : 4u;
-    // one walking wave per wbuf, kWalkWaves per workgroup
-    const int gw = (int)std::min<uint64_t>((nw + mcrc_dev::kWalkWaves - 1) / mcrc_dev::kWalkWaves, 65535);
-    const dim3 bw(64 * mcrc_dev::kWalkWaves);
-    mcrc_dev::WalkOut wo{};
-    wo.cnt = cnt;
-    // the count pass keeps each wbuf's first offsets (one per 2 KiB of wbuf:
-    // every 4 MiB wbuf of items of at least 2 KiB; 8 B per 2 KiB, 0.4 % of the
-    // walked bytes), so a K5 verify's emit pass copies them instead of walking
-    // again.  Wbufs under 16 KiB keep none (walked twice), and so does a walk
-    // whose slot buffer cannot be allocated.
-    wo.kslot = (uint32_t)std::min<uint64_t>(wbuf_bytes / 2048, 8192);
-    if (wo.kslot < 8) wo.kslot = 0;
-    wo.slots = wo.kslot ? d->walk_slots.reserve((size_t)nw * wo.kslot * 8) : nullptr;
-    if (!wo.slots) wo.kslot = 0;
-    HIP_OK(hipMemsetAsync(cnt + nw, 0, 4, st));
-    hipLaunchKernelGGL(mcrc_dev::k_walk<false>, dim3(gw), bw, 0, st, a, nw, wo);
-    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw + 1, prefix);
-    uint32_t total = 0;
-    HIP_OK(hipMemcpyAsync(&total, prefix + nw, 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
+    PageWalk w;
+    if ((rc = walk_count(*d, st, base, base_bytes, wbuf_bytes, nw, flags, &w))) return rc;
+    const uint32_t total = w.total;
     *nitems = total;
     if (total == 0 || cap == 0) {  // cap == 0: count-only query (no verify)
         *nbad = 0;
@@ -1678,34 +1809,9 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
     uint64_t *doffs = direct ? offsets : d->walk_offs.reserve((size_t)total * 8);
     uint8_t *dok = direct ? ok : d->walk_ok.reserve(total);
     if (!doffs || !dok) return CRC32C_ENOMEM;
-    a.offsets = doffs;
-    a.ok = dok;
-    a.n = total;
-    // The emit pass writes the offsets: copied from the count pass's slots,
-    // or for a wbuf of more items than those (or with no slots kept) by
-    // walking it again.  A planned verify then reads the headers in k_count,
-    // in parallel (round 6; the emit pass used to walk again and write
-    // k_count's entries itself, one header per round trip on mixed pages);
-    // only when no slots are kept does the second walk write the entries
-    // too (the headers are then read once more, not twice).
-    Path path;
-    path.small = takes_small<1>(a);
-    const bool k5 = !path.small && items_fused(a);  // (then the walk writes offsets only)
-    path.counted = !path.small && !k5 && wo.kslot == 0;
-    if (path.counted) {
-        rc = ensure_plan(*d, total, plan_cap(a));
-        if (rc) return rc;
-        a.span_acc = d->span_acc.get();
-    }
-    wo.prefix = prefix;
-    wo.offs = doffs;
-    wo.err = d->nbad + 1;
-    wo.nunit = path.counted ? d->nunit.get() : nullptr;
-    wo.irec = path.counted ? d->irec.get() : nullptr;
-    wo.fast = path.counted ? d->fast.get() : nullptr;
-    HIP_OK(hipMemsetAsync(d->nbad, 0, 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(mcrc_dev::k_walk<true>, dim3(gw), bw, 0, st, a, nw, wo);
-    rc = k5 ? launch_items<1>(*d, a, st) : launch_units<1>(*d, a, st, path);
+    w.a.ok = dok;
+    if ((rc = walk_emit(*d, st, &w, doffs, true))) return rc;
+    rc = w.k5 ? launch_items<1>(*d, w.a, st) : launch_units<1>(*d, w.a, st, w.path);
     if (rc) return rc;
     HIP_OK(hipMemcpyAsync(d->hbad, d->nbad, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     const uint64_t k = std::min<uint64_t>(cap, total);
@@ -1717,6 +1823,28 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
     HIP_OK(hipStreamSynchronize(st));
     *nbad = d->hbad[0];
     return d->hbad[1] ? CRC32C_EWALK : CRC32C_OK;
+}
+
+int crc32c_stamp_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint8_t *ok,
+                       uint64_t cap, uint64_t *nitems, uint64_t *nbad, unsigned flags, void *stream) {
+    if (!base || !wbuf_bytes || !nitems || !nbad || (cap && (!offsets || !ok))) return CRC32C_EINVAL;
+    Device *d = nullptr;
+    int rc = current_device(&d);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool dev = flags & CRC32C_DEVICE;
+    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
+    std::lock_guard<std::mutex> lk(d->mu);
+    const uint64_t nw = (base_bytes + wbuf_bytes - 1) / wbuf_bytes;
+    Lease lease(*d, st, !dev);  // (host: every exit drains st first, the copies write pinned scratch)
+    *nitems = *nbad = 0;
+    if (nw == 0 || nw >= 0x7fffffffull) return nw ? CRC32C_EINVAL : CRC32C_OK;
+    PageWalk w;
+    if ((rc = walk_count(*d, st, base, base_bytes, wbuf_bytes, nw, flags, &w))) return rc;
+    *nitems = w.total;
+    if (w.total == 0) return CRC32C_OK;
+    return (flags & CRC32C_KEEP_STAMPED) ? stamp_walked<3>(*d, st, w, base, dev, offsets, ok, cap, nbad)
+                                         : stamp_walked<2>(*d, st, w, base, dev, offsets, ok, cap, nbad);
 }
 
 int crc32c_shard_cuts(const uint32_t *lens, uint32_t len, uint64_t n, int parts, uint64_t *cuts) {

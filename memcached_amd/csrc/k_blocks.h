@@ -66,7 +66,7 @@ __global__ __launch_bounds__(1024) void k_blocks(SpanArgs a, const uint4 *__rest
     // A span here is one whole block and has a unit (one_block), so its block
     // is [Ea - 4096, Ea) whichever case of one_block holds.
     auto block_of = [&](const uint4 &r) -> const uint8_t * {
-        const uint64_t off = r.x | ((uint64_t)(r.y & ~kInsane) << 32);
+        const uint64_t off = rec_off(r);
         bool sane = !(r.y & kInsane);
         if (IDENT) sane = off <= a.base_bytes && r.z <= a.base_bytes - off;  // (as decode_unit)
         const uint8_t *e = a.base + off + r.z;

@@ -115,8 +115,9 @@ struct SpanArgs {
     uint32_t len;
     const uint32_t *crc_in;    // MODE 0: per-span initial CRC or nullptr (0)
     uint32_t *out;             // MODE 0: CRC per span
-    uint8_t *ok;               // MODE 1: 1 if the stored CRC matches
-    unsigned long long *nbad;  // MODE 1/2: count of mismatches / malformed images;
+    uint8_t *ok;               // MODE 1: 1 if the stored CRC matches; MODE 2/3 (optional): kItemStamped,
+                               // MODE 3: kItemKept for a carried image whose stored CRC matches
+    unsigned long long *nbad;  // MODE 1/2/3: count of mismatches / malformed images;
                                // MODE 0: spans outside [base, base + base_bytes) (atomic)
     uint64_t n;                // spans (items)
     const uint32_t *xpow;      // x^(8*j), x^(8*1024*j), x^(8*2^20*j) (3 x 1024), x^(-8t) (16),
@@ -152,8 +153,8 @@ __device__ __forceinline__ const uint4 *zero_slot(const SpanArgs &a) {
 struct ItemDesc {
     const uint8_t *p;
     uint32_t len;
-    uint32_t aux;  // MODE 0: initial CRC; MODE 1: stored CRC
-    bool sane;     // MODE 1: header parsed to an in-bounds span
+    uint32_t aux;  // MODE 0: initial CRC; MODE 1/2/3: stored CRC
+    bool sane;     // MODE 1/2/3: header parsed to an in-bounds span
 };
 
 // t = Ea - E: a span's grid ends at Ea = E rounded up to 16.  (Rounding up to
@@ -477,23 +478,45 @@ __device__ __forceinline__ ItemDesc fetch_item(const SpanArgs &a, uint64_t i) {
     return item_desc(a, off, h, hdr_ok);
 }
 
-// Item record written by k_count: {offset of the span (lo, hi | !sane << 31), len, z}:
+// Item record written by k_count: {offset of the span (lo, hi | flags), len, z}:
 // z = Z (span_corr; MODE 0 and 2) or, for a verify (MODE 1), W = Z ^ M_t(~stored CRC),
-// so that the stored CRC matches iff R == W.
-constexpr uint32_t kInsane = 0x80000000u;
+// so that the stored CRC matches iff R == W.  A keep-stamped stamp (MODE 3)
+// decides per image: W and kCarried for a carried image (stored CRC != 0),
+// Z for a fresh one.  The flags sit in the offset's top bits (rec_off).
+constexpr uint32_t kInsane = 0x80000000u;   // !sane
+constexpr uint32_t kCarried = 0x40000000u;  // MODE 3: verified, not stamped
+constexpr uint32_t kRecFlags = kInsane | kCarried;
+__device__ __forceinline__ uint64_t rec_off(const uint4 &r) { return r.x | ((uint64_t)(r.y & ~kRecFlags) << 32); }
 
-// Store (MODE 0) or stamp (MODE 2) the CRC of span `item`, which starts at p.
+// ok[] values of a stamp (CRC32C_ITEM_STAMPED / _KEPT, crc32c_batch.h).
+constexpr uint8_t kItemStamped = 1, kItemKept = 2;
+// MODE 3 (CRC32C_KEEP_STAMPED): an image whose stored CRC is not 0 was
+// carried over with it (compaction, storage.c:1004-1006): compared, not
+// stamped.
+template <int MODE>
+__device__ __forceinline__ bool carried_image(bool sane, uint32_t stored) {
+    return MODE == 3 && sane && stored != 0u;
+}
+
+// Store (MODE 0) or stamp (MODE 2/3) the CRC of span `item`, which starts at p.
 // Stamp writes the spill CRC into the image's exptime field, bytes 28..31 =
 // p - 4 (storage.c:567), or into out[] when the caller stages the images (host
 // path); ok[] (if any) marks stamped images.  A span that is not sane (outside
-// the buffer, or a malformed image) was not read (the caller counts it).
+// the buffer, or a malformed image) was not read.  MODE 3 writes nothing for
+// a carried image (stored: its exptime) and marks it kItemKept when crc equals
+// the stored value.  Returns whether the caller counts the span as bad.
 template <int MODE>
-__device__ __forceinline__ void emit(const SpanArgs &a, uint64_t item, uint32_t crc, bool sane, const uint8_t *p) {
+__device__ __forceinline__ bool emit(const SpanArgs &a, uint64_t item, uint32_t crc, bool sane, const uint8_t *p,
+                                     uint32_t stored = 0u) {
     if (MODE == 0) {
         a.out[item] = sane ? crc : 0u;
+    } else if (carried_image<MODE>(sane, stored)) {
+        const bool good = crc == stored;
+        if (a.ok) a.ok[item] = good ? kItemKept : 0;
+        return !good;
     } else {
         if (a.ok) a.ok[item] = sane;
-        if (!sane) return;
+        if (!sane) return true;
         if (a.out) {
             a.out[item] = crc;
         } else {
@@ -502,6 +525,7 @@ __device__ __forceinline__ void emit(const SpanArgs &a, uint64_t item, uint32_t 
             __builtin_memcpy(const_cast<uint8_t *>(p) - 4, &crc, 4);
         }
     }
+    return !sane;
 }
 
 // nb summed over the wave's 64 lanes, in every lane.

@@ -59,7 +59,8 @@ struct ItemsOut {
     uint32_t *fb;   // items for the planned path (sane, not one block)
     uint32_t *nfb;  // their count
     const uint32_t *route;  // k_census's verdict (nullptr: take the batch); 0: every image to the planned path
-    uint2 *rt;      // MODE 2: per item {M_t(f), t | kRtFused}, {0, 0} if not fused (for k_fix)
+    uint2 *rt;      // MODE 2/3: per item {M_t(f), t | kRtFused}, {0, 0} if not fused or (MODE 3)
+                    // a carried image, which k_lines itself verified (for k_fix)
     uint32_t xm128;      // k_lines: x^(-8 * 128) (MODE 0: the CRC from M_128(V))
     uint32_t nsr;        // k_lines: steps per run (a wave's run is 2 nsr consecutive images)
 };
@@ -96,8 +97,8 @@ struct ItemBuf {
 
 template <int MODE, bool OFFS>
 __global__ __launch_bounds__(1024) void k_lines(SpanArgs a, const uint4 *__restrict__ img, ItemsOut io) {
-    // MODE 0: equal spans of a.len bytes by offsets (OFFS) or stride, MODE 1/2:
-    // item images (verify / stamp) by offsets
+    // MODE 0: equal spans of a.len bytes by offsets (OFFS) or stride, MODE 1/2/3:
+    // item images (verify / stamp / stamp that keeps carried CRCs) by offsets
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const uint64_t n = a.n;
     const uint64_t nsr = io.nsr;
@@ -287,7 +288,15 @@ __global__ __launch_bounds__(1024) void k_lines(SpanArgs a, const uint4 *__restr
                     nb += !good;
                 }
             } else {
-                io.rt[item] = fused ? make_uint2(v, pad | kRtFused) : make_uint2(0u, 0u);
+                // MODE 3: a carried image (stored CRC != 0) is compared here as
+                // a verify's and gets no record, so k_fix writes nothing for it
+                const bool kept = fused && carried_image<MODE>(sane, p_stored);
+                if (kept) {
+                    const bool good = v == apply_op<4>(kAuxTree + 12, zeros_lds(~p_stored, pad, c));
+                    if (a.ok) a.ok[item] = good ? kItemKept : 0;
+                    nb += !good;
+                }
+                io.rt[item] = fused && !kept ? make_uint2(v, pad | kRtFused) : make_uint2(0u, 0u);
                 if (!sane) {
                     if (a.ok) a.ok[item] = 0;
                     ++nb;
@@ -356,13 +365,15 @@ __global__ __launch_bounds__(1024) void k_lines(SpanArgs a, const uint4 *__restr
     if (lane == 0 && nb) atomicAdd(a.nbad, (unsigned long long)nb);
 }
 
-// The last step of a K5 stamp (MODE 2), one thread per image: from W =
+// The last step of a K5 stamp (MODE 2/3), one thread per image: from W =
 // M_{t + 128}(f), f the register after the span from ~0, the CRC is
 // ~M_{-t-128}(W) (xm128 = x^(-8 * 128)), stamped into
 // the image's exptime as the spill CRC (storage.c:567).  A separate pass:
 // within k_lines an image's stamp could race with another wave's read of the
 // same bytes when images overlap.  (MODE 0 spans get their CRC from the epoch
-// lanes of k_lines itself.)
+// lanes of k_lines itself, and so do MODE 3's carried images their verdict:
+// they have no record here, so a wbuf of carried images costs no scattered
+// 4-B store at all.)
 __global__ void k_fix(SpanArgs a, const uint2 *rt, const uint32_t *route, uint32_t xm128) {
     MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
     if (route && *route == 0) return;  // (k_lines took no image)

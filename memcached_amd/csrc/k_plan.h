@@ -51,13 +51,15 @@ __device__ __forceinline__ void count_item(const SpanArgs &a, uint64_t i, const 
     nunit[i] = nu | (uint64_t)span_blocks(it.p, it.len, nu) << 32;
     const uint64_t off = (uint64_t)(it.p - a.base);
     uint32_t z = 0;
+    const bool carried = carried_image<MODE>(it.sane, it.aux);  // (MODE 3: k_final compares instead of stamping)
     if (it.sane) {
         // (a whole span's R from the wave, whole_chunks: z = R ^ Z of its pieces)
         z = corr_apply(span_corr_arg(it.p, it.len, MODE == 0 ? it.aux : 0u, t8, whole), t8, a.xpow) ^
             (whole ? rwhole : 0u);
-        if (MODE == 1) z ^= mulmodp_dev(~it.aux, a.xpow[grid_pad(it.p, it.len)]);  // W
+        if (MODE == 1 || carried) z ^= mulmodp_dev(~it.aux, a.xpow[grid_pad(it.p, it.len)]);  // W
     }
-    irec[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32) | (it.sane ? 0u : kInsane), it.len, z);
+    irec[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32) | (it.sane ? 0u : kInsane) | (carried ? kCarried : 0u),
+                         it.len, z);
     a.span_acc[i] = 0u;
 }
 
@@ -419,7 +421,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_expand(const uint8_t *base, co
                 } else {
                     // (one unit with the span's head rule: the same grid, so the same G1)
                     const uint4 r = irec[i];
-                    const uint64_t off = r.x | ((uint64_t)(r.y & ~kInsane) << 32);
+                    const uint64_t off = rec_off(r);
                     whole[atomicAdd(nwhole, 1u)] = make_unit(base, off, r.z, r.w, !(r.y & kInsane), (uint32_t)i, kWhole);
                 }
             }
@@ -454,7 +456,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_expand(const uint8_t *base, co
                 const uint64_t cki = nunit[i];
                 const uint32_t ns = (uint32_t)cki;
                 const uint4 r = irec[i];
-                const uint64_t off = r.x | ((uint64_t)(r.y & ~kInsane) << 32);
+                const uint64_t off = rec_off(r);
                 const uint32_t s0 = first_seg(base + off, r.z, ns);
                 const uint64_t nb0 = (cki >> 32) - (uint64_t)(kSegBytes / kBlockBytes) * (ns - 1);
                 const uint64_t bs = b0 + (j ? nb0 + (uint64_t)(j - 1) * (kSegBytes / kBlockBytes) : 0u);
@@ -479,7 +481,7 @@ __global__ void k_expand_big(const uint8_t *base, const uint64_t *nunit, const P
         const uint64_t p0 = e.y, b0 = e.z | ((uint64_t)e.w << 32);
         const uint32_t ns = (uint32_t)nunit[i];
         const uint4 r = irec[i];
-        const uint64_t off = r.x | ((uint64_t)(r.y & ~kInsane) << 32);
+        const uint64_t off = rec_off(r);
         const bool sane = !(r.y & kInsane);
         const uint32_t s0 = first_seg(base + off, r.z, ns);
         // every unit after the first is a whole segment
@@ -492,7 +494,8 @@ __global__ void k_expand_big(const uint8_t *base, const uint64_t *nunit, const P
 
 // Every span's result from its R (one thread per span):
 //   planned (UNITS): R = span_acc[i], z from the item record: MODE 1 checks
-//   R == W, MODE 0/2 compute ~M_{-t}(R ^ Z);
+//   R == W, MODE 0/2 compute ~M_{-t}(R ^ Z), MODE 3 does either by the
+//   record's kCarried;
 //   one unit per span (MODE 0, no plan): R = out[i], Z computed here.
 template <int MODE, bool UNITS>
 __global__ void k_final(SpanArgs a, const uint4 *irec) {
@@ -505,10 +508,11 @@ __global__ void k_final(SpanArgs a, const uint4 *irec) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint8_t *p;
         uint32_t len, R, z = 0;
-        bool sane;
+        bool sane, carried = false;
         if (UNITS) {
             const uint4 r = irec[i];
-            p = a.base + (r.x | ((uint64_t)(r.y & ~kInsane) << 32));
+            carried = MODE == 3 && (r.y & kCarried);
+            p = a.base + rec_off(r);
             sane = !(r.y & kInsane);
             len = r.z;
             z = r.w;
@@ -526,12 +530,15 @@ __global__ void k_final(SpanArgs a, const uint4 *irec) {
             const bool good = sane && R == z;
             a.ok[i] = good;
             nb += !good;
+        } else if (carried) {  // (sane; nothing is written to the image)
+            const bool good = R == z;
+            if (a.ok) a.ok[i] = good ? kItemKept : 0;
+            nb += !good;
         } else {
             const uint32_t t = grid_pad(p, len);
             uint32_t v = R ^ z;
             if (t) v = mulmodp_dev(v, a.xpow[kXpowInv + t]);
-            emit<MODE>(a, i, ~v, sane, p);
-            nb += !sane;
+            nb += emit<MODE>(a, i, ~v, sane, p);
         }
     }
     count_bad(a.nbad, nb);

@@ -84,8 +84,7 @@ __global__ __launch_bounds__(1024) void k_small(SpanArgs a, const uint4 *__restr
         } else {
             uint32_t v = R ^ z;
             if (t) v = mulmodp_dev(v, a.xpow[kXpowInv + t]);
-            if (li == 0) emit<MODE>(a, i, ~v, it.sane, it.p);
-            nb = li == 0 && !it.sane;
+            nb = li == 0 && emit<MODE>(a, i, ~v, it.sane, it.p, it.aux);  // (MODE 3: it.aux decides)
         }
     }
     // one atomic per wave with a bad span (all 160 KiB of LDS hold the tables,

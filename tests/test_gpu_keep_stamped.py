@@ -1,0 +1,410 @@
+"""CRC32C_KEEP_STAMPED and crc32c_stamp_pages on the GPU: wbufs that mix fresh
+images (exptime 0) with images carried over with their stored CRC, through
+every route a stamp can take (k_small, the planned path, K5 and its fallback
+list, the host paths).  Every comparison is exact -- the whole buffer byte for
+byte, every ok value and nbad -- against the CPU model of
+tests/keep_stamped_model.py (the oracle's CRCs; nothing from the library)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+try:  # GPU processes load torch (and its HIP runtime) before libmcrc32c.so
+    import torch as _torch  # noqa: F401
+except ImportError:
+    pass
+
+from memcached_amd import _lib, layout
+from memcached_amd import crc32c as mc
+
+from . import keep_stamped_model as model
+from . import oracle
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True, params=["small", "planned"])
+def span_path(request):
+    """Every case runs twice: batches of at most 8192 images through the
+    single-launch k_small (the default) and through the planned path
+    (crc32c_set_small_max(0)); larger batches take K5 either way."""
+    prev = _lib.lib.crc32c_set_small_max(0 if request.param == "planned" else 8192)
+    yield request.param
+    _lib.lib.crc32c_set_small_max(prev)
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
+    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
+    return t
+
+
+def _dev(torch, arr):
+    return torch.from_numpy(np.array(arr)).cuda()  # (a writable copy: the fixtures are read-only)
+
+
+def _crcs(buf, offs, cfl=4):
+    return np.array([oracle.item_crc(buf, o, cfl) for o in offs], np.uint32)
+
+
+def _carry(buf, offs, which, cfl=4):
+    """Make the images `which` carried ones: their spill CRC in exptime."""
+    crcs = _crcs(buf, offs[which], cfl)
+    assert (crcs != 0).all()  # (a stored 0 would read as fresh)
+    layout.store_crcs(buf, offs[which], crcs)
+
+
+def _stamp(torch, where, buf, offs, wbuf, keep, cflags64=False):
+    """stamp_items on a copy of buf held on the device, in pageable host memory
+    or in a crc32c_host_alloc buffer: (bytes after, ok, nbad)."""
+    if where == "device":
+        d = _dev(torch, buf)
+        ok, nbad = mc.stamp_items(d, _dev(torch, offs.view(np.int64)), region_bytes=wbuf, keep_stamped=keep,
+                                  cflags64=cflags64)
+        torch.cuda.synchronize()
+        return d.cpu().numpy(), ok.cpu().numpy(), nbad
+    if where == "host":
+        h = buf.copy()
+        ok, nbad = mc.stamp_items(h, offs, region_bytes=wbuf, keep_stamped=keep, cflags64=cflags64)
+        return h, ok, nbad
+    p = _lib.lib.crc32c_host_alloc(buf.size)
+    assert p
+    try:
+        arr = np.ctypeslib.as_array((ctypes.c_uint8 * buf.size).from_address(p))
+        arr[:] = buf
+        ok, nbad = mc.stamp_items(arr, offs, region_bytes=wbuf, keep_stamped=keep, cflags64=cflags64)
+        return arr.copy(), ok, nbad
+    finally:
+        _lib.lib.crc32c_host_free(p)
+
+
+def _check(got, want):
+    (g_buf, g_ok, g_bad), (w_buf, w_ok, w_bad) = got, want
+    np.testing.assert_array_equal(g_ok, w_ok)
+    assert g_bad == w_bad
+    np.testing.assert_array_equal(g_buf, w_buf)
+
+
+# -- case 1: a mixed wbuf on the small and planned routes ----------------------
+
+WBUF = 1 << 20
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    """900 images with values of 0..9000 B in 1 MiB wbufs (the shape of
+    test_stamp_items): by i % 3 fresh, carried, carried; every 10th carried
+    image has a flipped data bit, one carried image a flipped nbytes bit, one
+    fresh image nkey = 0."""
+    rng = np.random.default_rng(371)
+    items = [layout.make_item(b"ks%06d" % i, rng.integers(0, 256, int(rng.integers(0, 9000)), dtype=np.uint8).tobytes(),
+                              cas=i + 1) for i in range(900)]
+    buf, offs = layout.pack_wbufs(items, WBUF)
+    carried = np.array([i for i in range(900) if i % 3])
+    _carry(buf, offs, carried)
+    damaged = carried[::10]
+    for i in damaged.tolist():
+        o, nt = int(offs[i]), layout.ntotal_of(buf, int(offs[i]))
+        buf[o + 48 + int(rng.integers(0, nt - 48))] ^= 1 << int(rng.integers(0, 8))
+    lenbit = 401
+    assert lenbit % 3 and lenbit not in damaged
+    buf[int(offs[lenbit]) + 34] ^= 0x10  # nbytes += 1 MiB: the image leaves its wbuf
+    nokey = 300
+    buf[int(offs[nokey]) + 41] = 0
+    buf.flags.writeable = False
+    return buf, offs, set(damaged.tolist()) | {lenbit, nokey}
+
+
+@pytest.mark.parametrize("where", ["device", "host", "pinned"])
+def test_mixed_wbuf(torch, mixed, where):
+    buf, offs, bad = mixed
+    want = model.expected_stamp(buf, offs, WBUF, keep=True)
+    assert set(np.flatnonzero(want[1] == 0).tolist()) == bad and (want[1] == 2).sum() == 600 - len(bad) + 1
+    got = _stamp(torch, where, buf, offs, WBUF, keep=True)
+    _check(got, want)
+    # the read-back verify: bad exactly the damaged carried images and the malformed ones
+    ok, nbad = mc.verify_items(got[0], offs, region_bytes=WBUF)
+    np.testing.assert_array_equal(ok, model.expected_verify(want[0], offs, WBUF))
+    assert set(np.flatnonzero(ok == 0).tolist()) == bad and nbad == len(bad)
+    # without the flag nothing changed: every sane image is stamped (the damage laundered)
+    _check(_stamp(torch, where, buf, offs, WBUF, keep=False), model.expected_stamp(buf, offs, WBUF, keep=False))
+
+
+# -- case 2: K5 with its fallback list -----------------------------------------
+
+@pytest.fixture(scope="module")
+def k5_pages():
+    """The 6000-image pages of test_k5_verify_stamp_and_walk_with_fallback:
+    4165-B images, every 50th of another size, 1 MiB wbufs; exptime 0."""
+    rng = np.random.default_rng(55)
+    n = 6000
+    vals = [4096 if i % 50 else int(rng.integers(200, 9000)) for i in range(n)]
+    items = [layout.make_item(b"key%07d" % i, rng.integers(0, 256, v, dtype=np.uint8).tobytes(), cas=i + 1)
+             for i, v in enumerate(vals)]
+    buf, offs = layout.pack_wbufs(items, WBUF)
+    buf.flags.writeable = False
+    return buf, offs
+
+
+def _k5_variant(k5_pages, variant):
+    clean, offs = k5_pages
+    buf = clean.copy()
+    n = offs.size
+    if variant == "fresh":
+        return buf
+    carried = np.arange(n) if variant == "carried" else np.array([i for i in range(n) if i % 3])
+    _carry(buf, offs, carried)
+    if variant == "mixed":
+        rng = np.random.default_rng(56)
+        for k, i in enumerate(rng.choice(carried, 100, replace=False).tolist()):
+            o = int(offs[i])
+            if k % 10 == 9:
+                buf[o + 32 + int(rng.integers(0, 2))] ^= 1 << int(rng.integers(0, 8))  # a length bit: off K5's shape
+            elif k % 2:
+                buf[o + 40] ^= 0x40  # slabs_clsid: in the span, the header stays sane
+            else:
+                buf[o + 48 + int(rng.integers(0, layout.ntotal_of(buf, o) - 48))] ^= 1 << int(rng.integers(0, 8))
+    return buf
+
+
+@pytest.mark.parametrize("variant", ["mixed", "fresh", "carried"])
+def test_k5_with_fallback(torch, k5_pages, variant):
+    offs = k5_pages[1]
+    buf = _k5_variant(k5_pages, variant)
+    want = model.expected_stamp(buf, offs, WBUF, keep=True)
+    if variant == "mixed":
+        assert want[2] == 100
+    else:
+        assert want[2] == 0 and (want[1] == (1 if variant == "fresh" else 2)).all()
+    _check(_stamp(torch, "device", buf, offs, WBUF, keep=True), want)
+
+
+# -- case 3: K5 runs longer than one step --------------------------------------
+
+def test_k5_full_epochs(torch):
+    n, nt = 3 * 8192 + 5, 4165
+    g = torch.Generator(device="cuda").manual_seed(13)
+    d = torch.randint(0, 256, (n * nt + 64,), dtype=torch.uint8, device="cuda", generator=g)
+    im = d[:n * nt].view(n, nt)
+    # memcached.h:613-636 header: nbytes 4098, it_flags ITEM_CAS, nkey 10 -> ITEM_ntotal 4165; exptime zeroed
+    im[:, 28:32] = 0
+    im[:, 32:36] = torch.tensor([4098 & 255, 4098 >> 8, 0, 0], dtype=torch.uint8, device="cuda")
+    im[:, 38:40] = torch.tensor([2, 0], dtype=torch.uint8, device="cuda")
+    im[:, 41] = 10
+    offs = np.arange(n, dtype=np.uint64) * nt
+    doffs = _dev(torch, offs.view(np.int64))
+    ok, nbad = mc.stamp_items(d, doffs)
+    assert nbad == 0 and bool(ok.all())
+    fresh = np.arange(0, n, 4)
+    im[torch.from_numpy(fresh).cuda(), 28:32] = 0
+    carried = np.setdiff1d(np.arange(n), fresh)
+    victims = carried[::1000]
+    im[torch.from_numpy(victims).cuda(), 2000] ^= 0x40
+    before = d.cpu().numpy()
+    want_buf, want_ok, want_bad = model.expected_stamp(before, offs, 0, keep=True)
+    assert want_bad == victims.size and (want_ok[fresh] == 1).all()
+    ok, nbad = mc.stamp_items(d, doffs, keep_stamped=True)
+    torch.cuda.synchronize()
+    _check((d.cpu().numpy(), ok.cpu().numpy(), nbad), (want_buf, want_ok, want_bad))
+    np.testing.assert_array_equal(np.flatnonzero(want_ok == 0), victims)
+
+
+# -- case 4: long images (several work units) ----------------------------------
+
+@pytest.mark.parametrize("where", ["device", "host"])
+def test_long_images(torch, where):
+    rng = np.random.default_rng(372)
+    big = [layout.make_item(b"lg%05d" % i, rng.integers(0, 256, int(rng.integers(65000, 400000)),
+                                                        dtype=np.uint8).tobytes(), cas=i + 1) for i in range(30)]
+    buf, offs = layout.pack_wbufs(big, WBUF)
+    carried = np.arange(1, 30, 2)
+    _carry(buf, offs, carried)
+    v = int(carried[7])
+    buf[int(offs[v]) + layout.ntotal_of(buf, int(offs[v])) - 10] ^= 0x02  # in the image's last unit
+    want = model.expected_stamp(buf, offs, WBUF, keep=True)
+    assert want[2] == 1 and want[1][v] == 0
+    _check(_stamp(torch, where, buf, offs, WBUF, keep=True), want)
+
+
+# -- case 5: client-flags width ------------------------------------------------
+
+@pytest.mark.parametrize("cfl", [4, 8])
+def test_client_flags_width(torch, cfl):
+    rng = np.random.default_rng(100 + cfl)
+    wbuf = 128 * 1024
+    items = [layout.make_item(b"key%07d" % i, rng.integers(0, 256, int(rng.integers(0, 3000)), dtype=np.uint8).tobytes(),
+                              cas=i + 1 if i % 5 else None,
+                              client_flags=(0x1_0000_0003 if cfl == 8 else 0x3) * (i % 2), cflags_bytes=cfl)
+             for i in range(400)]
+    buf, offs = layout.pack_wbufs(items, wbuf)
+    carried = np.array([i for i in range(400) if i % 3])
+    _carry(buf, offs, carried, cfl)
+    for i in carried[::25].tolist():
+        buf[int(offs[i]) + 40] ^= 0x01
+    want = model.expected_stamp(buf, offs, wbuf, keep=True, cfl=cfl)
+    assert want[2] == len(carried[::25])
+    for where in ("device", "host"):
+        _check(_stamp(torch, where, buf, offs, wbuf, keep=True, cflags64=cfl == 8), want)
+
+
+# -- case 6: crc32c_stamp_pages ------------------------------------------------
+
+def _stamp_pages(torch, where, buf, wbuf, keep, size=None):
+    """stamp_pages over the first `size` bytes of a copy of buf: (bytes after
+    (all of buf), offsets, ok, nbad)."""
+    size = buf.size if size is None else size
+    if where == "device":
+        d = _dev(torch, buf)
+        o, ok, nbad = mc.stamp_pages(d[:size], wbuf, keep_stamped=keep)
+        torch.cuda.synchronize()
+        return d.cpu().numpy(), o.cpu().numpy().astype(np.uint64), ok.cpu().numpy(), nbad
+    h = buf.copy()
+    o, ok, nbad = mc.stamp_pages(h[:size], wbuf, keep_stamped=keep)
+    return h, o.copy(), ok.copy(), nbad
+
+
+def _check_pages(torch, where, buf, wbuf, keep, size=None):
+    """stamp_pages == the model over a host walk's offsets == stamp_items over
+    those offsets."""
+    size = buf.size if size is None else size
+    h_offs = model.host_walk(buf[:size], wbuf)
+    w_head, w_ok, w_bad = model.expected_stamp(buf[:size], h_offs, wbuf, keep)
+    want_buf = np.concatenate([w_head, buf[size:]])  # nothing behind `size` is touched
+    g_buf, g_offs, g_ok, g_bad = _stamp_pages(torch, where, buf, wbuf, keep, size)
+    np.testing.assert_array_equal(g_offs, h_offs)
+    _check((g_buf, g_ok, g_bad), (want_buf, w_ok, w_bad))
+    i_buf, i_ok, i_bad = _stamp(torch, where, np.ascontiguousarray(buf[:size]), h_offs, wbuf, keep)
+    _check((g_buf[:size], g_ok, g_bad), (i_buf, i_ok, i_bad))
+    return h_offs, w_ok
+
+
+@pytest.mark.parametrize("keep", [True, False])
+@pytest.mark.parametrize("where", ["device", "host"])
+def test_stamp_pages_mixed_wbuf(torch, mixed, where, keep):
+    h_offs, _ = _check_pages(torch, where, mixed[0], WBUF, keep)
+    assert h_offs.size < mixed[1].size  # (the nkey = 0 image ends its wbuf's walk)
+
+
+@pytest.mark.parametrize("keep", [True, False])
+@pytest.mark.parametrize("where", ["device", "host"])
+def test_stamp_pages_k5_with_fallback(torch, k5_pages, where, keep):
+    _check_pages(torch, where, _k5_variant(k5_pages, "mixed"), WBUF, keep)
+
+
+def test_stamp_pages_small_wbufs_walked_twice(torch):
+    """K5-shaped images in 8 KiB wbufs, which keep no walk slots: the emit pass
+    walks every wbuf again."""
+    rng = np.random.default_rng(8 << 10)
+    items = [layout.make_item(b"key%07d" % i, rng.integers(0, 256, 4096, dtype=np.uint8).tobytes(), cas=i + 1)
+             for i in range(4200)]
+    buf, offs = layout.pack_wbufs(items, 8 << 10)
+    carried = np.array([i for i in range(4200) if i % 3])
+    _carry(buf, offs, carried)
+    for i in carried[::100].tolist():
+        buf[int(offs[i]) + 100 + int(rng.integers(0, 3000))] ^= 1 << int(rng.integers(0, 8))
+    for where in ("device", "host"):
+        h_offs, w_ok = _check_pages(torch, where, buf, 8 << 10, True)
+        np.testing.assert_array_equal(h_offs, offs)
+        assert (w_ok == 0).sum() == len(carried[::100])
+
+
+@pytest.mark.parametrize("where", ["device", "host"])
+def test_stamp_pages_walk_stop_partial_wbuf_and_open_wbuf(torch, mixed, where):
+    clean, offs, _ = mixed
+    # a length bit that ends one wbuf's walk: the images behind it are not
+    # stamped, not counted and byte-identical to before
+    buf = clean.copy()
+    k = 40
+    assert k % 3 == 1 and int(offs[k + 30]) < WBUF
+    buf[int(offs[k]) + 34] ^= 0x20  # nbytes += 2 MiB: the next header lies past the wbuf
+    h_offs, w_ok = _check_pages(torch, where, buf, WBUF, True)
+    assert int(h_offs[k]) == int(offs[k]) and w_ok[k] == 0 and int(h_offs[k + 1]) == WBUF
+    got = _stamp_pages(torch, where, buf, WBUF, True)[0]
+    np.testing.assert_array_equal(got[int(offs[k]):WBUF], buf[int(offs[k]):WBUF])
+    assert (k + 2) % 3 == 0 and not got[int(offs[k + 2]) + 28:int(offs[k + 2]) + 32].any()  # (a fresh one: unstamped)
+    # a partial last wbuf that cuts an image: found by the walk, malformed
+    cut = int(offs[-1]) + 60
+    h_offs, w_ok = _check_pages(torch, where, np.ascontiguousarray(clean[:cut]), WBUF, True)
+    assert int(h_offs[-1]) == int(offs[-1]) and w_ok[-1] == 0 and cut % WBUF
+    # an open wbuf: base_bytes = the bytes used, non-zero garbage behind them
+    used = int(offs[120])
+    assert used < WBUF
+    open_wbuf = clean[:WBUF].copy()
+    open_wbuf[used:] = 0xa5
+    open_wbuf[used + 41::97] = 7  # (would parse as images)
+    h_offs, _ = _check_pages(torch, where, open_wbuf, WBUF, True, size=used)
+    np.testing.assert_array_equal(h_offs, offs[:120])
+
+
+@pytest.mark.parametrize("where", ["device", "host"])
+def test_stamp_pages_cap_below_nitems_and_zero(torch, mixed, where):
+    buf = mixed[0]
+    h_offs = model.host_walk(buf, WBUF)
+    want_buf, want_ok, want_bad = model.expected_stamp(buf, h_offs, WBUF, keep=True)
+    fl = _lib.CRC32C_KEEP_STAMPED | (_lib.CRC32C_DEVICE if where == "device" else 0)
+    for cap in (100, 0):
+        nitems, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if where == "device":
+            b = _dev(torch, buf)
+            o = torch.full((cap + 8,), -1, dtype=torch.int64, device="cuda")
+            k = torch.full((cap + 8,), 9, dtype=torch.uint8, device="cuda")
+            ptrs = (b.data_ptr(), o.data_ptr(), k.data_ptr())
+        else:
+            b = buf.copy()
+            o = np.full(cap + 8, 2 ** 64 - 1, np.uint64)
+            k = np.full(cap + 8, 9, np.uint8)
+            ptrs = (b.ctypes.data, o.ctypes.data, k.ctypes.data)
+        _lib.check(_lib.lib.crc32c_stamp_pages(ptrs[0], buf.size, WBUF, ptrs[1] if cap else None,
+                                               ptrs[2] if cap else None, cap, ctypes.byref(nitems), ctypes.byref(nbad),
+                                               fl, None), "crc32c_stamp_pages")
+        if where == "device":
+            torch.cuda.synchronize()
+            b, o, k = b.cpu().numpy(), o.cpu().numpy().view(np.uint64), k.cpu().numpy()
+        assert nitems.value == h_offs.size and nbad.value == want_bad
+        np.testing.assert_array_equal(b, want_buf)  # everything is stamped
+        np.testing.assert_array_equal(o[:cap], h_offs[:cap])
+        np.testing.assert_array_equal(k[:cap], want_ok[:cap])
+        assert (o[cap:] == 2 ** 64 - 1).all() and (k[cap:] == 9).all()  # nothing past cap is written
+
+
+# -- case 7: async -------------------------------------------------------------
+
+def test_async_keep_stamped(torch, k5_pages):
+    offs = k5_pages[1]
+    buf = _k5_variant(k5_pages, "mixed")
+    want = model.expected_stamp(buf, offs, WBUF, keep=True)
+    for n in (offs.size, 700):  # K5 with its fallback list, and a small / planned batch
+        d = _dev(torch, buf)
+        do = _dev(torch, offs.view(np.int64))
+        st = torch.cuda.current_stream()
+        _lib.check(_lib.lib.crc32c_stamp_items(d.data_ptr(), d.numel(), WBUF, do.data_ptr(), n, None, None,
+                                               _lib.CRC32C_DEVICE | _lib.CRC32C_ASYNC | _lib.CRC32C_KEEP_STAMPED,
+                                               ctypes.c_void_p(st.cuda_stream)), "async stamp")
+        st.synchronize()
+        w = want[0] if n == offs.size else model.expected_stamp(buf, offs[:n], WBUF, keep=True)[0]
+        np.testing.assert_array_equal(d.cpu().numpy(), w)
+
+
+# -- case 8: exact bad counts across small-route calls -------------------------
+
+@pytest.mark.parametrize("where", ["device", "host"])
+def test_small_route_bad_counts_exact_across_calls(torch, mixed, where):
+    """k_small hands its count to the host through its last workgroup and
+    leaves the counter at zero: consecutive calls with different bad counts
+    each report exactly their own."""
+    prev = _lib.lib.crc32c_set_small_max(8192)
+    try:
+        buf, offs, bad = mixed
+        worse = buf.copy()
+        extra = [i for i in range(2, 900, 7) if i % 3 and i not in bad]
+        for i in extra:
+            worse[int(offs[i]) + 40] ^= 0x10
+        wants = [model.expected_stamp(b, offs, WBUF, keep=True) for b in (buf, worse)]
+        assert wants[0][2] == len(bad) and wants[1][2] == len(bad) + len(extra)
+        for rep in range(3):
+            for b, want in zip((buf, worse), wants):
+                _check(_stamp(torch, where, b, offs, WBUF, keep=True), want)
+    finally:
+        _lib.lib.crc32c_set_small_max(prev)
