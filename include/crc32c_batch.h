@@ -24,6 +24,10 @@
  *                          (walk of storage.c:950-960): CRC over
  *                          [off + 32, off + ITEM_ntotal) against the value
  *                          stored in the item's exptime field (byte 28).
+ *   crc32c_copy_items      the rescue copy of storage_compact_readback
+ *                          (storage.c:1004-1006), which the reference makes
+ *                          unchecked: every image compaction keeps is moved to
+ *                          its new place and verified from the same loads.
  *   crc32c_host_alloc      pinned buffers for wbufs / readback_buf (SURVEY.md 8f
  *                          rank 3).
  *   crc32c_batch_multi     crc32c_batch for host-resident batches split across
@@ -80,6 +84,11 @@ extern "C" {
  * CRC does not match) */
 #define CRC32C_ITEM_STAMPED 1 /* the CRC was written into exptime */
 #define CRC32C_ITEM_KEPT 2    /* CRC32C_KEEP_STAMPED: the stored CRC matched, nothing written */
+
+/* ok[] values of crc32c_copy_items (0: nothing written -- a malformed source
+ * image, or one that does not fit dst) */
+#define CRC32C_ITEM_COPIED 1  /* written to dst, stored CRC matches */
+#define CRC32C_ITEM_DAMAGED 3 /* written to dst verbatim, stored CRC does not match */
 
 /* Longest span: 2 GiB - 64 KiB, twice the largest item memcached stores
  * (ITEM_SIZE_MAX_UPPER_LIMIT, memcached.h:115).  A device span past it is not
@@ -217,6 +226,52 @@ int crc32c_stamp_items(void *base, uint64_t base_bytes, uint64_t region_bytes,
 int crc32c_stamp_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets,
                        uint8_t *ok, uint64_t cap, uint64_t *nitems, uint64_t *nbad, unsigned flags,
                        void *stream);
+
+/* Copy n item images and verify them while they pass: the copy that
+ * storage_compact_readback makes of every image it keeps (storage.c:1004-1006,
+ * unchecked in the reference), given as the list of images the walk decided to
+ * rescue (src_offsets, into [src, src + src_bytes)) and the places
+ * extstore_write_request gave them (dst_offsets, into [dst, dst + dst_bytes)).
+ * Each image is read once: the 16-byte pieces the CRC folds are the pieces
+ * that are stored.
+ *   Sanity.  Image i is judged sane exactly as crc32c_verify_items judges it;
+ *     src_bytes, region_bytes and CRC32C_CFLAGS64 apply to the source.
+ *   A sane image that fits.  With nt = ITEM_ntotal, the bytes
+ *     [src + src_offsets[i], + nt) are written to [dst + dst_offsets[i], + nt),
+ *     all nt of them, header bytes 0..31 included, and
+ *     c = crc32c(0, image + 32, nt - 32) is computed from the same loads:
+ *     ok[i] = CRC32C_ITEM_COPIED when c == exptime, else CRC32C_ITEM_DAMAGED.  A
+ *     damaged image is still written in full (its verdict is known only after
+ *     its last byte has passed).  In dst it keeps its mismatching CRC, so a later
+ *     read still counts it (storage.c:160-178), and it is walk-consistent there
+ *     (it advances the walk by its own nt); the caller must not relink the item
+ *     to it.
+ *   An image that is not sane.  Nothing is written, ok[i] = 0, counted bad.
+ *   A sane image that does not fit (dst_offsets[i] + nt > dst_bytes).  Nothing is
+ *     written, ok[i] = 0, counted bad, and the call returns CRC32C_ERANGE (an
+ *     asynchronous call cannot report it, as with crc32c_batch).
+ *   *nbad counts every image whose ok is not CRC32C_ITEM_COPIED.
+ *   No stray writes.  No byte of dst outside the written images is written, not
+ *     even with the value it already holds (neighbouring images are written
+ *     concurrently); no byte of src is written.
+ *   Placement is the caller's.  The library does not pack; destination images
+ *     must not overlap each other; [src, + src_bytes) and [dst, + dst_bytes)
+ *     must not overlap (CRC32C_EINVAL when they do); region_bytes is not applied
+ *     to dst.
+ * Host or device per flags, as for crc32c_stamp_items: with CRC32C_DEVICE src,
+ * dst, both offset arrays and ok are device memory, and with CRC32C_DEVICE |
+ * CRC32C_ASYNC and nbad == NULL the call returns once the work is enqueued on
+ * `stream`.  Host buffers that are both page-locked (crc32c_host_alloc /
+ * _register: the readback_buf and the wbufs) are read and written in place by
+ * the GPU; otherwise the images are verified on the GPU and copied by the host.
+ * NULL src, dst, src_offsets, dst_offsets or ok: CRC32C_EINVAL; n == 0:
+ * CRC32C_OK with *nbad = 0; no device: CRC32C_ENODEV, nothing written.  The
+ * destination wbuf must not be submitted before the call returns (or, for an
+ * asynchronous call, before `stream` has passed it). */
+int crc32c_copy_items(const void *src, uint64_t src_bytes, uint64_t region_bytes,
+                      const uint64_t *src_offsets, void *dst, uint64_t dst_bytes,
+                      const uint64_t *dst_offsets, uint64_t n, uint8_t *ok, uint64_t *nbad,
+                      unsigned flags, void *stream);
 
 /* Asynchronous form of crc32c_batch: returns at once with a job handle;
  * crc32c_batch_wait blocks until out[] is filled and frees the handle.

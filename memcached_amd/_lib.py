@@ -28,6 +28,8 @@ CRC32C_CFLAGS64 = 0x8
 CRC32C_KEEP_STAMPED = 0x10
 CRC32C_ITEM_STAMPED = 1  # ok[] values of the stamp calls
 CRC32C_ITEM_KEPT = 2
+CRC32C_ITEM_COPIED = 1  # ok[] values of crc32c_copy_items
+CRC32C_ITEM_DAMAGED = 3
 CRC32C_MAX_SPAN = 0x7FFF0000  # longest span (include/crc32c_batch.h)
 
 # every symbol include/*.h declares (checked by tests/test_abi.py)
@@ -37,7 +39,7 @@ EXPORTED = (
     "crc32c_verify_pages", "crc32c_batch_chains", "crc32c_host_alloc", "crc32c_host_free",
     "crc32c_batch_submit", "crc32c_batch_wait", "crc32c_strerror", "crc32c_last_kernel_ms",
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
-    "crc32c_set_small_max", "crc32c_stamp_pages",
+    "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items",
 )
 
 
@@ -94,6 +96,12 @@ def _load():
     if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_stamp_pages"):  # (an A/B against an older build)
         lib.crc32c_stamp_pages.restype = ctypes.c_int
         lib.crc32c_stamp_pages.argtypes = lib.crc32c_verify_pages.argtypes
+    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_copy_items"):  # (an A/B against an older build)
+        lib.crc32c_copy_items.restype = ctypes.c_int
+        lib.crc32c_copy_items.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint,
+                                          ctypes.c_void_p]
     lib.crc32c_batch_chains.restype = ctypes.c_int
     lib.crc32c_batch_chains.argtypes = [ctypes.POINTER(Spans), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_uint, ctypes.c_void_p]

@@ -9,6 +9,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``verify_items`` stored-CRC check of packed item images (storage.c:160-178)
 * ``stamp_items``  spill CRC written into each image's exptime (storage.c:567)
 * ``stamp_pages``  walk + stamp whole wbufs on the device (no offset list)
+* ``copy_items``   compaction's rescue copy, verified while it copies (storage.c:1004-1006)
 * ``verify_pages`` walk + verify whole pages on the device (storage.c:950-1070)
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
@@ -27,6 +28,7 @@ from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
+           "copy_items",
            "batch_multi",
            "shard_cuts", "queue_stats", "set_small_max", "gpu_count", "Crc32cError"]
 
@@ -213,6 +215,60 @@ def stamp_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False, 
         rc = lib.crc32c_stamp_items(buf.ctypes.data, buf.size, region_bytes, offs.ctypes.data, offs.size,
                                     ok.ctypes.data, ctypes.byref(nbad), fl, None)
     check(rc, "crc32c_stamp_items")
+    return ok, int(nbad.value)
+
+
+def copy_items(src, src_offsets, dst, dst_offsets, region_bytes=0, stream=None, cflags64=False):
+    """Copy the item images at ``src_offsets`` of ``src`` to ``dst_offsets`` of
+    ``dst`` and verify them from the same loads (compaction's rescue copy,
+    storage.c:1004-1006, checked).  Returns (ok, nbad): ok[i] is 1 for an image
+    written whose stored CRC matches, 3 for one written verbatim whose stored
+    CRC does not match, 0 when nothing was written (a malformed image, or one
+    that does not fit ``dst``: the call then raises Crc32cError(CRC32C_ERANGE)
+    after the other images are copied, with ok and nbad as attributes of the
+    error); nbad counts every ok that is not 1.
+
+    ``src`` and ``dst`` are both torch device tensors (the call runs on the
+    current stream) or both host buffers, ``dst`` a writable contiguous uint8
+    numpy array; ``region_bytes`` and ``cflags64`` apply to the source, as for
+    verify_items."""
+    dev = _is_torch(src) and src.is_cuda
+    if dev != (_is_torch(dst) and dst.is_cuda):
+        raise ValueError("copy_items: src and dst must both be device tensors or both be host buffers")
+    nbad = ctypes.c_uint64(0)
+    fl = CRC32C_CFLAGS64 if cflags64 else 0
+    if dev:
+        import torch
+        if not (src.is_contiguous() and dst.is_contiguous()):
+            raise ValueError("copy_items: need contiguous device tensors")
+        n = src_offsets.numel()
+        _check_dev(src_offsets, "src_offsets", n, ("int64", "uint64"))
+        _check_dev(dst_offsets, "dst_offsets", n, ("int64", "uint64"))
+        ok = torch.empty(n, dtype=torch.uint8, device=src.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(src.device).cuda_stream
+        rc = lib.crc32c_copy_items(src.data_ptr(), src.numel() * src.element_size(), region_bytes,
+                                   src_offsets.data_ptr(), dst.data_ptr(), dst.numel() * dst.element_size(),
+                                   dst_offsets.data_ptr(), n, ok.data_ptr(), ctypes.byref(nbad), CRC32C_DEVICE | fl,
+                                   stream)
+    else:
+        if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.writeable
+                and dst.flags.c_contiguous):
+            raise TypeError("copy_items needs a writable contiguous uint8 numpy array as dst (written in place)")
+        src = _host_buf(src)
+        soffs = np.ascontiguousarray(src_offsets, dtype=np.uint64)
+        doffs = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        if doffs.size != soffs.size:
+            raise ValueError(f"dst_offsets: {doffs.size} elements for {soffs.size} images")
+        ok = np.empty(soffs.size, dtype=np.uint8)
+        rc = lib.crc32c_copy_items(src.ctypes.data, src.size, region_bytes, soffs.ctypes.data, dst.ctypes.data,
+                                   dst.size, doffs.ctypes.data, soffs.size, ok.ctypes.data, ctypes.byref(nbad), fl,
+                                   None)
+    if rc == _lib.CRC32C_ERANGE:  # everything that fits is copied: the verdicts travel with the error
+        err = Crc32cError(rc, "crc32c_copy_items")
+        err.ok, err.nbad = ok, int(nbad.value)
+        raise err
+    check(rc, "crc32c_copy_items")
     return ok, int(nbad.value)
 
 

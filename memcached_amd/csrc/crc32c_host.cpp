@@ -1,8 +1,11 @@
 // crc32c_host.cpp -- host CRC-32C used by the scalar drop-in symbol.
 #include "crc32c_host.h"
 
+#include <string.h>
+
 #include <mutex>
 
+#include "../../include/crc32c_batch.h"
 #include "crc32c_gf2.h"
 
 #if defined(__x86_64__)
@@ -185,6 +188,29 @@ uint32_t crc32c_host_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
     // crc(A||B) = ~(M_|B|(~crc(A)) ^ raw(B)), raw(B) = ~crc_b ^ M_|B|(~0)
     // => crc(A||B) = M_|B|(crc_a) ^ crc_b   (the ~ terms cancel by linearity)
     return mulmodp(crc_a, xpow8n(len_b)) ^ crc_b;
+}
+
+uint64_t item_ntotal(const uint8_t *it, uint32_t cfl) {
+    uint32_t nbytes;
+    uint16_t flags;
+    memcpy(&nbytes, it + 32, 4);
+    memcpy(&flags, it + 38, 2);
+    return 48ull + it[41] + 1 + nbytes + ((flags & 256u) ? cfl : 0) + ((flags & 2u) ? 8 : 0);
+}
+
+bool item_sane(const uint8_t *base, uint64_t base_bytes, uint64_t region, uint64_t off, uint32_t cfl,
+               uint64_t *ntotal) {
+    *ntotal = 0;
+    if (off > base_bytes || base_bytes - off < 48) return false;
+    const uint8_t *it = base + off;
+    uint32_t nbytes;
+    memcpy(&nbytes, it + 32, 4);
+    const uint64_t nt = item_ntotal(it, cfl);
+    const bool in_region = region == 0 || off / region == (off + nt - 1) / region;
+    if (it[41] == 0 || nbytes >= 0x80000000u || nt - 32 > CRC32C_MAX_SPAN || nt > base_bytes - off || !in_region)
+        return false;
+    *ntotal = nt;
+    return true;
 }
 
 }  // namespace mcrc

@@ -22,4 +22,15 @@ bool host_has_hw_crc();  // SSE4.2 (x86-64) or the ARMv8 CRC extension (arm64)
 // crc32c(crc, A || B) from crc32c(crc, A), crc32c(0, B) and |B|.
 uint32_t crc32c_host_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
+// The item header rule of the device code (mcrc_dev::ItemHdr / item_desc,
+// k_common.h) restated for the host: ITEM_ntotal of the image at `it`
+// (memcached.h:149-152; cfl = sizeof(client_flags_t)), and whether the image at
+// base + off is sane -- its 48 header bytes lie in [base, base + base_bytes),
+// nkey != 0, nbytes < 2^31, its span is at most CRC32C_MAX_SPAN, and it ends
+// inside the buffer and inside its own `region` (0: no such bound).  *ntotal:
+// ITEM_ntotal of a sane image, else 0.
+uint64_t item_ntotal(const uint8_t *it, uint32_t cfl);
+bool item_sane(const uint8_t *base, uint64_t base_bytes, uint64_t region, uint64_t off, uint32_t cfl,
+               uint64_t *ntotal);
+
 }  // namespace mcrc

@@ -22,6 +22,8 @@
 //     lane of a run of consecutive images; k_fix stamps (MODE 2).
 //     k_small: batches of up to 8192 spans in one launch (IO batches, wbufs,
 //     the coalescing queue).
+//     k_copy: k_small's verify with every block also stored at the image's
+//     destination (crc32c_copy_items: compaction's rescue copy, checked).
 //
 // See crc32c_device.h for the lane-group work model and LDS table layouts.
 //
@@ -32,6 +34,7 @@
 #include "k_spans.h"   // K2/K3: work units, k_spans
 #include "k_plan.h"    // K2/K3: k_count, the plan's scans, k_expand, k_final
 #include "k_small.h"   // k_small
+#include "k_copy.h"    // k_copy: crc32c_copy_items (copy and verify in one pass)
 #include "k_window.h"  // K1Regs / k1_lane_value: the whole window of K4 and K5
 #include "k_blocks.h"  // K4
 #include "k_lines.h"   // K5: k_lines, k_fix, k_census

@@ -117,7 +117,7 @@ struct Device {
     // k_small's own counters for calls that take the count from hbad (item
     // images): zero between calls, kept so by the kernel's last workgroup
     unsigned long long *small_nbad = nullptr;
-    uint32_t *small_done = nullptr;
+    uint32_t *small_done = nullptr;  // ([1]: k_copy's count of images that did not fit dst, kept the same way)
     uint32_t *nfb = nullptr;    // k_lines' fallback count (device)
     uint32_t *route = nullptr;  // k_census's verdict: K5 (1) or the planned path (0)
     hipStream_t stream = nullptr, copy = nullptr;
@@ -316,6 +316,7 @@ int init_device(Device &d, int id) {
         (const void *)mcrc_dev::k_small<1>,
         (const void *)mcrc_dev::k_small<2>,
         (const void *)mcrc_dev::k_small<3>,
+        (const void *)mcrc_dev::k_copy,
         (const void *)mcrc_dev::k_blocks<false, true>,
         (const void *)mcrc_dev::k_blocks<true, true>,
         (const void *)mcrc_dev::k_blocks<true, false>,
@@ -1100,6 +1101,126 @@ int item_images(void *base, uint64_t base_bytes, uint64_t region_bytes, const ui
     return CRC32C_OK;
 }
 
+// k_copy over a's images on st: enough workgroups to reach every CU, groups
+// per workgroup as launch_small chooses them; past one image per group the
+// groups stride over the list.  The counts arrive in d.hbad[0] (bad images)
+// and d.hbad[1] (sane images that did not fit dst) from the kernel's last
+// workgroup, which leaves the device counters at zero.
+int launch_copy(const Device &d, mcrc_dev::SpanArgs a, mcrc_dev::CopyArgs ca, hipStream_t st) {
+    const uint64_t cus = (uint64_t)std::max(d.cus, 1);
+    uint64_t per = (a.n + cus - 1) / cus;
+    per = std::min<uint64_t>(32, std::max<uint64_t>(8, (per + 1) & ~1ull));
+    const uint64_t grid = std::min<uint64_t>((a.n + per - 1) / per, cus);
+    a.nbad = d.small_nbad;
+    a.done = d.small_done;
+    a.host_nbad = d.hbad;
+    ca.nrange = d.small_done + 1;
+    hipLaunchKernelGGL(mcrc_dev::k_copy, dim3((unsigned)grid), dim3((unsigned)(32 * per)), mcrc_dev::kLdsImageK1Bytes,
+                       st, a, ca, d.img);
+    HIP_OK(hipGetLastError());
+    return CRC32C_OK;
+}
+
+bool ranges_overlap(const void *p, uint64_t pn, const void *q, uint64_t qn) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return pn && qn && a < b + qn && b < a + pn;
+}
+
+// crc32c_copy_items.
+//   device: k_copy in place on the caller's stream;
+//   host, both buffers page-locked and mapped (crc32c_host_alloc / _register:
+//     extstore's readback_buf and wbufs): the same kernel reads and writes
+//     them through their mapped addresses on the library stream; offsets and
+//     ok through pinned mapped scratch;
+//   host, otherwise: the verdicts come from the host verify route
+//     (item_images<1>) and the host copies the sane images that fit with
+//     memcpy -- bytes already in host memory cross the link once, for the
+//     check, and not again for the copy.
+int copy_items(const void *src, uint64_t src_bytes, uint64_t region_bytes, const uint64_t *src_offsets, void *dst,
+               uint64_t dst_bytes, const uint64_t *dst_offsets, uint64_t n, uint8_t *ok, uint64_t *nbad,
+               unsigned flags, void *stream) {
+    if (!src || !dst || !src_offsets || !dst_offsets || !ok) return CRC32C_EINVAL;
+    if (ranges_overlap(src, src_bytes, dst, dst_bytes)) return CRC32C_EINVAL;
+    Device *d = nullptr;
+    int rc = current_device(&d);
+    if (rc) return rc;
+    if (n == 0) {
+        if (nbad) *nbad = 0;
+        return CRC32C_OK;
+    }
+    const bool dev = flags & CRC32C_DEVICE;
+    const uint32_t cfl = (flags & CRC32C_CFLAGS64) ? 8u : 4u;
+    mcrc_dev::SpanArgs a = common_args(*d);
+    a.base_bytes = src_bytes;
+    a.n = n;
+    a.region = region_bytes;
+    a.cfl = cfl;
+    mcrc_dev::CopyArgs ca{};
+    ca.dst_bytes = dst_bytes;
+    if (dev) {
+        if (!device_range_ok(src, src_bytes) || !device_range_ok(dst, dst_bytes)) return CRC32C_EINVAL;
+        std::lock_guard<std::mutex> lk(d->mu);
+        hipStream_t st = (hipStream_t)stream;  // NULL: the default stream
+        a.base = (const uint8_t *)src;
+        a.offsets = src_offsets;
+        a.ok = ok;
+        ca.dst = (uint8_t *)dst;
+        ca.dst_offsets = dst_offsets;
+        {
+            Lease lease(*d, st);
+            if ((rc = launch_copy(*d, a, ca, st))) return rc;
+        }
+        if ((flags & CRC32C_ASYNC) && !nbad) return CRC32C_OK;  // fire and forget
+        HIP_OK(hipStreamSynchronize(st));
+        if (nbad) *nbad = d->hbad[0];
+        return d->hbad[1] ? CRC32C_ERANGE : CRC32C_OK;
+    }
+    const uint8_t *const msrc = device_view_range(src, src_bytes);
+    const uint8_t *const mdst = msrc ? device_view_range(dst, dst_bytes) : nullptr;
+    if (msrc && mdst) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        hipStream_t st = d->stream;
+        HIP_OK(hipSetDevice(d->id));
+        Lease lease(*d, st, true);  // (every exit drains st first: the kernel writes pinned scratch)
+        uint64_t *const h_offs = d->pin_offs.reserve(2 * n * 8);
+        uint8_t *const h_ok = d->pin_ok.reserve(n);
+        if (!h_offs || !h_ok) return CRC32C_ENOMEM;
+        memcpy(h_offs, src_offsets, n * 8);
+        memcpy(h_offs + n, dst_offsets, n * 8);
+        a.base = msrc;
+        a.offsets = d->pin_offs.dev();
+        a.ok = d->pin_ok.dev();
+        ca.dst = const_cast<uint8_t *>(mdst);
+        ca.dst_offsets = d->pin_offs.dev() + n;
+        if ((rc = launch_copy(*d, a, ca, st))) return rc;
+        HIP_OK(hipStreamSynchronize(st));
+        memcpy(ok, h_ok, n);
+        if (nbad) *nbad = d->hbad[0];
+        return d->hbad[1] ? CRC32C_ERANGE : CRC32C_OK;
+    }
+    uint64_t nv = 0;
+    if ((rc = item_images<1>(const_cast<void *>(src), src_bytes, region_bytes, src_offsets, n, ok, &nv,
+                             flags & ~(unsigned)CRC32C_ASYNC, nullptr)))
+        return rc;
+    uint64_t bad = 0;
+    bool range = false;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t nt = 0;
+        const bool sane = mcrc::item_sane((const uint8_t *)src, src_bytes, region_bytes, src_offsets[i], cfl, &nt);
+        const bool fits = dst_offsets[i] <= dst_bytes && nt <= dst_bytes - dst_offsets[i];
+        if (sane && fits) {
+            memcpy((uint8_t *)dst + dst_offsets[i], (const uint8_t *)src + src_offsets[i], nt);
+            ok[i] = ok[i] ? CRC32C_ITEM_COPIED : CRC32C_ITEM_DAMAGED;
+        } else {
+            ok[i] = 0;
+            range |= sane;
+        }
+        bad += ok[i] != CRC32C_ITEM_COPIED;
+    }
+    if (nbad) *nbad = bad;
+    return range ? CRC32C_ERANGE : CRC32C_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1779,6 +1900,13 @@ int crc32c_stamp_items(void *base, uint64_t base_bytes, uint64_t region_bytes, c
     if (flags & CRC32C_KEEP_STAMPED)
         return item_images<3>(base, base_bytes, region_bytes, item_offsets, n, ok, nbad, flags, stream);
     return item_images<2>(base, base_bytes, region_bytes, item_offsets, n, ok, nbad, flags, stream);
+}
+
+int crc32c_copy_items(const void *src, uint64_t src_bytes, uint64_t region_bytes, const uint64_t *src_offsets,
+                      void *dst, uint64_t dst_bytes, const uint64_t *dst_offsets, uint64_t n, uint8_t *ok,
+                      uint64_t *nbad, unsigned flags, void *stream) {
+    return copy_items(src, src_bytes, region_bytes, src_offsets, dst, dst_bytes, dst_offsets, n, ok, nbad, flags,
+                      stream);
 }
 
 int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint8_t *ok,
