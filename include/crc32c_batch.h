@@ -120,7 +120,8 @@ typedef struct crc32c_spans {
     uint64_t n;
 } crc32c_spans;
 
-/* Number of usable gfx950 devices (0 when none). */
+/* Number of usable gfx950 devices (0 when none): the visible HIP ordinals
+ * that are gfx950, whatever other devices sit between them. */
 int crc32c_gpu_count(void);
 
 /* Checksum a batch.  Host batches are staged through pinned memory and the
@@ -129,8 +130,10 @@ int crc32c_gpu_count(void);
  * call returns when they are done. */
 int crc32c_batch(const crc32c_spans *spans, unsigned flags, void *stream);
 
-/* Host batch split across the first `ngpus` devices by bytes; one host thread
- * per device, pinned H2D / D2H overlapped with the kernels. */
+/* Host batch split by bytes into `ngpus` parts (<= 0 or more than there are:
+ * crc32c_gpu_count()); part g runs on the g-th gfx950 device in HIP ordinal
+ * order, on that device's persistent worker thread, pinned H2D / D2H
+ * overlapped with the kernels. */
 int crc32c_batch_multi(const crc32c_spans *spans, int ngpus);
 
 /* The split crc32c_batch_multi uses: parts + 1 cut points, part g owns spans

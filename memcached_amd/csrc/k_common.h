@@ -4,6 +4,7 @@
 #pragma once
 
 #include "crc32c_device.h"
+#include "k_consts.h"
 
 namespace mcrc_dev {
 
@@ -37,10 +38,6 @@ __device__ __forceinline__ uint4 ld16_nt(gbyte *p) {
 __device__ __forceinline__ uint32_t dw4(const uint4 &v, int k) {
     return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w;
 }
-
-// K1 geometry: a 32-lane group owns one 4096-B item, a wave two items per
-// step.
-constexpr uint32_t kK1Bytes = 4096;
 
 // K1's lane layout (round 5).  A 32-lane group owns one 4096-B item, and lane
 // i holds the 16-B pieces at 512 k + 16 i, k = 0..7: each load instruction
@@ -82,18 +79,6 @@ static_assert(kK1Pieces * kK1Piece == 4096 && 32 * kK1LaneBytes == kK1Piece, "K1
 // round 5 the thread also read F_t and XORed raw(F_t) into Z: a line per
 // span that the span kernel reads again.)
 
-constexpr uint32_t kRowBytes = 1024;  // a row: two of K1's 512-B piece rows (the head-block skip)
-constexpr uint32_t kBlockBytes = 4 * kRowBytes;  // 4096
-// (round 5: 128 KiB; config 3 -1.1..-1.3 % against 64 KiB in two sessions, the
-// mixed pages and config 5 within noise, 256 KiB like 128 --
-// profiles/r05_ablations/segment_size_ab.txt; rounds 1-3 found 24-64 KiB alike)
-constexpr uint32_t kSegBytes = 128 * 1024;
-// Longest span (CRC32C_MAX_SPAN): a unit's grid offsets (eo, G - p, the block
-// count times 4 KiB) are 32-bit and signed, and a span that overlaps others
-// past the plan's capacity is one unit.  Twice the largest item memcached
-// stores (ITEM_SIZE_MAX_UPPER_LIMIT = 1 GiB, memcached.h:115).  Longer spans
-// are not read (out = 0, counted as out of range / malformed).
-constexpr uint32_t kMaxSpan = 0x7fff0000u;
 constexpr uint32_t kWhole = 0xffffffffu;      // unit segment index: the whole span
 // Pieces outside a span are read from a zeroed buffer; workgroup b reads the
 // 16 B at zero + 4 KiB * (b % 256), so the workgroups' zero reads spread over
@@ -166,11 +151,6 @@ constexpr uint32_t kTailAlign = 16;
 __device__ __forceinline__ uint32_t tail_pad(const uint8_t *p, uint32_t len) {
     return (uint32_t)(-(uintptr_t)(p + len)) & (kTailAlign - 1);
 }
-// The planned path's grid (round 5): anchored at Ea = E rounded up to a
-// 128-B line, so every block of a unit is whole lines and the span kernel's
-// non-temporal loads never share a line between two instructions; the
-// span's thread folds up to 127 foreign tail bytes instead of 15.
-constexpr uint32_t kGridAlign = 128;
 __device__ __forceinline__ uint32_t grid_pad(const uint8_t *p, uint32_t len) {
     return (uint32_t)(-(uintptr_t)(p + len)) & (kGridAlign - 1);
 }
@@ -311,17 +291,7 @@ __device__ __forceinline__ uint32_t reg_advance(uint32_t r, const uint8_t *p, ui
 // (The limits are measured: a thread's chain is serial, one LDS round trip
 // per 16 B, so long fragments cost more than the block step they save --
 // DESIGN.md section 3.)
-constexpr uint32_t kFragMax = 128;    // a head fragment [p, G1) of at most this
-// (512 since round 5: 256-512 beat 1024 by 1.0-1.3 % on the mixed pages and
-// matched it on config 3; 2048 / 3072 were 1-3 % slower --
-// profiles/r05_ablations/whole_span_limit_ab.txt)
-constexpr uint32_t kWholeMax = 512;   // a whole span of vlen at most this
 static_assert(kWholeMax + kGridAlign <= kBlockBytes, "a whole span held by its thread is its own fragment (G1 = Ea)");
-// Is the head fragment (G1 - p = g1o) the span thread's?  For vlen <= kWholeMax
-// the fragment is the whole span (G1 = Ea).
-__device__ __forceinline__ bool frag_drop(uint32_t len, uint64_t g1o, uint64_t vlen) {
-    return len != 0 && (g1o <= kFragMax || vlen <= kWholeMax);
-}
 struct SpanHead {
     uint64_t g1o;  // G1 - p
     bool drop;     // [p, G1) is the thread's

@@ -42,18 +42,11 @@
 
 namespace mcrc_dev {
 
-constexpr uint32_t kLineBytes = 128;
 constexpr uint32_t kHeadPieces = 10;  // 16-B pieces of [floor16(p), A): A - p <= 131
 constexpr uint32_t kTailPieces = 9;   // of [B, Et): Et - B < 128 + 16
 constexpr uint32_t kSt31 = 0x80u;     // the window holds 31 lines (row 3, lanes 28-31: zeros)
 constexpr uint32_t kStFused = 0x10u, kStSane = 0x20u, kStValid = 0x40u;
-constexpr uint32_t kEpoch = 32;                                 // steps per epoch: 64 images per wave
 
-// The fused shape: B - A (bytes of whole lines inside the span after the
-// head) is 31 or 32 lines.
-__host__ __device__ __forceinline__ bool lines_fused(int64_t lines_bytes) {
-    return lines_bytes >= (int64_t)(kBlockBytes - kLineBytes) && lines_bytes <= (int64_t)kBlockBytes;
-}
 
 struct ItemsOut {
     uint32_t *fb;   // items for the planned path (sane, not one block)

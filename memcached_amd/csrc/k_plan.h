@@ -178,7 +178,6 @@ struct PlanSum {
     uint64_t units, blocks;
     uint32_t fast, pad;
 };
-constexpr uint32_t kPlanThreads = 1024, kPlanPer = 2, kPlanTile = kPlanThreads * kPlanPer;
 
 __device__ __forceinline__ PlanSum plan_of(uint64_t nu, uint8_t f) {
     return {(uint32_t)nu, nu >> 32, (uint32_t)f, 0u};

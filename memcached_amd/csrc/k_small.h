@@ -13,7 +13,6 @@ namespace mcrc_dev {
 // seven launches (count, scan, expand, span kernel x 2, final) cost ~80 us per
 // call whatever the batch; a storage.c wbuf stamp (1007 images) or an IO-batch
 // verify is one call of this kernel.
-constexpr uint32_t kSmallMax = 8192;
 
 // Register after the 16 bytes of v from a zero register, on the span image's
 // replicated slice-by-4 tables (this lane's copy).

@@ -255,11 +255,6 @@ __device__ __forceinline__ uint32_t mul_row_group(uint32_t v0, uint32_t xi, uint
     return term;
 }
 
-// 16 waves per CU (128 VGPRs).  768 threads (168 VGPRs) measured slower
-// (config 3: 5.99 vs 5.90 ms; config 5: 6.90 vs 5.93 ms per 300 pages):
-// latency hiding of the dependent lookup chains needs the waves.
-constexpr uint32_t kSpanBlock = 1024;
-
 // The span kernel: R = raw([ph, e)) of every work unit, pieces as they lie.
 // A unit that is a whole span stores R (span_acc[span], or out[span] without
 // a plan); a segment unit XORs M_{64Ki * (nseg-1-s)}(R) into span_acc[span].
@@ -285,7 +280,7 @@ __global__ __launch_bounds__(kSpanBlock) void k_spans(SpanArgs a, const uint4 *_
     // Rounds (round 5): the balanced plan cuts the batch's blocks into
     // rounds x G equal shares in block order and group g takes shares g,
     // G + g, 2G + g, ..., so the groups stream through one round's range of
-    // the batch (about 8 GiB: crc32c_shim.hip plan_rounds) at a time instead
+    // the batch (about 8 GiB: host_route.h plan_rounds) at a time instead
     // of each through its own 1/G of all of it.  Each round restarts the
     // group's pipeline.
     const uint32_t nrounds = bal ? a.rounds : 1u;

@@ -72,7 +72,6 @@ __global__ void k_chain(const uint32_t *iov_crc, const uint32_t *lens, uint32_t 
 // equal-sized items cost one round trip per 64 of them.  Round 6: after a
 // round trip whose guesses broke at lane 0 or 1 the next one guesses once
 // (lane 0 alone reads a header), and widens again when that guess holds.
-constexpr uint32_t kWalkWaves = 4;  // waves (wbufs) per workgroup
 
 struct WalkOut {
     uint32_t *cnt;           // count pass: items per wbuf

@@ -4,7 +4,7 @@ Items are independent, so a batch is split into contiguous index ranges, one
 per GPU, balanced by bytes (prefix sum of span lengths), not by count -- Zipf
 sized batches put most bytes in a few large items.  No collective is needed on
 the data path: each rank checksums its range and writes its slice of out[].
-The same split is implemented in C++ by crc32c_batch_multi (crc32c_shim.hip).
+The same split is implemented in C++ by crc32c_batch_multi (csrc/host_route.h shard_cuts).
 """
 from __future__ import annotations
 

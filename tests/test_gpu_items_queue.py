@@ -281,7 +281,7 @@ def test_eight_threads_concurrent_device_batches(torch):
     once (thread t on device t % device_count: every device where the box has
     several), mixing K1 items, unaligned spans and async calls, many rounds:
     the per-call device lookup takes no process-wide lock after the first call
-    (crc32c_shim.hip current_device) and no batch sees another's scratch.
+    (shim_device.h current_device) and no batch sees another's scratch.
     Every CRC against the oracle."""
     ng = torch.cuda.device_count()
     rng = np.random.default_rng(88)

@@ -606,7 +606,7 @@ def test_config3_full_size(torch, span_path):
 
 
 def test_planned_rounds_past_16_gib(torch, span_path):
-    """The balanced plan's rounds (crc32c_shim.hip plan_rounds: one per 8 GiB
+    """The balanced plan's rounds (host_route.h plan_rounds: one per 8 GiB
     of the batch's buffer, k_spans restarting every group's pipeline per
     round) on a 17 GiB device buffer: 3 rounds, each cutting its third of the
     plan's blocks (span order) into one share per span-kernel group.  Spans

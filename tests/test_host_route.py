@@ -1,0 +1,59 @@
+"""The host shim's decisions (memcached_amd/csrc/host_route.h: which kernels a
+batch goes to, the launch geometry, the plan's rounds and capacity, the host
+pipeline's staging order and chunk cuts, the shard cuts), checked on the CPU:
+tests/integration/host_route_check.cpp compiles the header as plain C++ under
+the address and undefined-behaviour sanitizers and asserts every boundary; this
+module recomputes from the Python models what the program prints."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from memcached_amd import shard
+from tests import span_model
+from tests.test_items_lines_model import lines_shape
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("host_route") / "host_route_check")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-I", os.path.join(ROOT, "memcached_amd", "csrc"),
+                    os.path.join(HERE, "integration", "host_route_check.cpp"), "-o", out], check=True)
+    return out
+
+
+def test_host_route_decisions(exe):
+    """Every assertion of the program (routes of fixed-length, small and item
+    batches, geometry, pipeline cuts), and its two fixed-length sets against
+    the models: K5 takes the lengths that lines_shape calls fused at all 128
+    alignments, k_blocks those that one_block calls one block (with a unit)
+    at all 128."""
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "host_route ok" in r.stdout
+    sets = {line.split()[0]: [int(x) for x in line.split()[1:]] for line in r.stdout.splitlines()[:2]}
+    k5 = [n for n in range(9001) if n >= 4 and all(lines_shape(al, n)[2] for al in range(128))]
+    blocks = [n for n in range(9001)
+              if all(span_model.one_block(al, n)[0] and not span_model.one_block(al, n)[1] for al in range(128))]
+    assert k5 == list(range(4099, 4228)) and sets["k5"] == k5
+    # (K5 is tested first; its lengths and k_blocks' are disjoint anyway)
+    assert blocks == list(range(4081, 4098)) and sets["blocks"] == blocks
+
+
+@pytest.mark.parametrize("parts", range(1, 9))
+def test_shard_cuts_match_plan(exe, parts):
+    """crc32c_shard_cuts' body against memcached_amd/shard.py plan() on the
+    same lengths: Zipf-like, equal, empty, zeros and one dominant span."""
+    rng = np.random.default_rng(parts)
+    cases = [rng.zipf(1.3, 1000).clip(1, 1 << 20), np.full(1000, 4096), np.zeros(0, dtype=np.int64),
+             np.zeros(7, dtype=np.int64), np.array([5, 0, 0, 1 << 30, 3, 3]), rng.integers(0, 1 << 32, 257)]
+    for lens in cases:
+        r = subprocess.run([exe, "cuts", str(parts)], input=" ".join(str(int(x)) for x in lens),
+                           capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert [int(x) for x in r.stdout.split()] == list(shard.plan(lens, parts))

@@ -191,7 +191,7 @@ def lines_runs(n, W, w, nsr):
 def test_line_runs_cover_every_image_once(n, grid):
     """Every image is taken by exactly one lane of one step of one run and
     runs hold at most 2 nsr <= 64 images (one per lane); nsr as launch_k5
-    (crc32c_shim.hip) sets it."""
+    (host_route.h k5_nsr) sets it."""
     W = grid * 16
     nsr = min(32, max(1, (n + 2 * W - 1) // (2 * W)))
     seen = np.zeros(n, dtype=np.int32)
