@@ -19,6 +19,11 @@
  *                          CRC32C_KEEP_STAMPED the images compaction copied with
  *                          their CRC (storage.c:1004-1006) are verified, not
  *                          stamped again.
+ *   crc32c_salvage_pages   the images of a page that the walk never reaches because
+ *                          a damaged header in front of them ended it
+ *                          (storage.c:950-1072 loses them silently): every
+ *                          unreached offset tried as an image start, the ones
+ *                          whose stored CRC proves them reported.
  *   crc32c_verify_items    the read-verify compare of storage.c:159-178 applied
  *                          to every item image of a packed extstore page
  *                          (walk of storage.c:950-960): CRC over
@@ -63,6 +68,7 @@ extern "C" {
 #define CRC32C_EWALK (-6)  /* crc32c_verify_pages / _stamp_pages: the device walk's count and emit
                               passes disagreed on some wbuf (an internal invariant;
                               the results are not valid) */
+#define CRC32C_EWORK (-7)  /* crc32c_salvage_pages: the candidates' spans exceed the work bound */
 
 /* flags */
 #define CRC32C_DEVICE 0x1u    /* every pointer in the batch is device memory of the
@@ -179,6 +185,78 @@ int crc32c_batch_chains(const crc32c_spans *iovs, const uint64_t *chain_first, u
 int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes,
                         uint64_t *offsets, uint8_t *ok, uint64_t cap, uint64_t *nitems,
                         uint64_t *nbad, unsigned flags, void *stream);
+
+/* Find the intact images behind a damaged header.  The page walk finds images
+ * one from the other, so one flipped header bit (nkey -> 0, a wrong nbytes or
+ * it_flags) costs every image packed behind it in that wbuf, almost all of
+ * them intact.  This call looks at every offset the walk's good images do not
+ * cover as a possible image start and reports those whose stored CRC matches.
+ *
+ * The rule.  W = wbuf_bytes, cfl = 4 (8 with CRC32C_CFLAGS64); piece w is
+ * [w W, min((w + 1) W, base_bytes)), as in crc32c_verify_pages.  For an offset o:
+ *   sane(o)       what crc32c_verify_items requires of a header: at least 48
+ *                 bytes left, nkey != 0, nbytes < 2^31, a span of at most
+ *                 CRC32C_MAX_SPAN, the image (nt = ITEM_ntotal bytes) inside the
+ *                 buffer and inside its own piece;
+ *   candidate(o)  sane(o), nbytes >= 2 and the image's last two bytes "\r\n"
+ *                 (every value memcached stores ends so; against random bytes a
+ *                 plausible header passes once per 2^10 offsets of a 4 MiB wbuf,
+ *                 with the CRLF once per 2^26);
+ *   intact(o)     candidate(o) and crc32c(0, base + o + 32, nt - 32) equal to
+ *                 the exptime field at o + 28.
+ * The covered set C: every entry of walked[0, nwalked) with walked_ok[i] != 0
+ * and sane(walked[i]) covers [walked[i], walked[i] + nt); an entry marked good
+ * whose header is not sane covers nothing.  The lists are what
+ * crc32c_verify_pages returned for the same buffer; with nwalked == 0 nothing is
+ * covered and every intact image of the buffer is found from scratch.  Per
+ * piece, from its first byte, while piece_end - o >= 48:
+ *     o in C          ->  o = the end of the covering image
+ *     else intact(o)  ->  report o;  o += nt
+ *     else            ->  o += 1
+ * The offsets reported are ascending, mutually disjoint and start outside every
+ * covered image; a candidate inside a reported image is never reported.  A
+ * look-alike inside the damaged image's own bytes can be: the caller's key
+ * lookup with its offset check (storage.c:964-975) makes that, and a 2^-32 CRC
+ * collision, harmless.
+ *   *scanned (optional) = the eligible offsets: those o of any piece with
+ *     piece_end - o >= 48 and o not in C;
+ *   *ncand (optional) = the eligible offsets with candidate(o);
+ *   both are exact and do not depend on how the search is carried out.
+ * The work bound.  With work = the sum of nt - 32 over the eligible candidates,
+ * work > CRC32C_SALVAGE_WORK_MAX * (scanned + W) verifies and reports nothing:
+ * CRC32C_EWORK with *nfound = 0, *scanned and *ncand filled.  True images are
+ * disjoint (at most `scanned` bytes in all) and real data yields less than one
+ * false candidate per wbuf; only values crafted as overlapping fake headers
+ * come near the bound, which keeps one call from becoming minutes of kernel
+ * time.  Treat such a wbuf as the reference does.  (More than 2^32 - 2
+ * candidates, possible only in such a buffer of several GiB, are refused the
+ * same way.)
+ * Outputs.  *nfound = the images found; the first min(cap, *nfound) offsets are
+ * written to offsets[], nothing behind them; cap == 0 counts only (the CRCs are
+ * still checked) and offsets may be NULL.
+ * With CRC32C_DEVICE base, walked, walked_ok and offsets are device memory (the
+ * three counts are always host words) and the call runs on `stream`; without
+ * it everything is host memory and the buffer is staged as crc32c_verify_pages
+ * stages it.  The counts are read back, so CRC32C_ASYNC has no effect.
+ * CRC32C_EINVAL: NULL base or nfound, wbuf_bytes == 0, cap != 0 with NULL
+ * offsets, nwalked != 0 with either list NULL, walked not strictly ascending or
+ * an entry >= base_bytes (nothing is written; so base_bytes == 0 with a list that
+ * is not empty), 2^31 - 1 pieces or more, 2^32 - 1 list entries or more.
+ * base_bytes == 0 with nwalked == 0: CRC32C_OK with zero counts; no device:
+ * CRC32C_ENODEV, nothing written.  Whatever the buffer
+ * or the lists hold, no byte outside [base, base + base_bytes) is read beyond
+ * the 16-byte granules of header bytes that the walk's own header reads touch,
+ * and nothing but the outputs is written.  After the call
+ * crc32c_last_kernel_ms() is the time of the scan's first pass over the
+ * eligible bytes, the one that counts the candidates (0 when nothing was
+ * eligible); the pass that writes them out reads the tiles that hold one again
+ * and is not in it.  Scratch (grow-only): 24 B per 4 KiB of eligible bytes, 13 B per
+ * candidate. */
+#define CRC32C_SALVAGE_WORK_MAX 64
+int crc32c_salvage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes,
+                         const uint64_t *walked, const uint8_t *walked_ok, uint64_t nwalked,
+                         uint64_t *offsets, uint64_t cap, uint64_t *nfound, uint64_t *scanned,
+                         uint64_t *ncand, unsigned flags, void *stream);
 
 /* Stamp the spill CRC of n item images (storage.c:567, gathered per wbuf
  * before it is submitted): exptime (bytes 28..31) of image i receives
@@ -325,7 +403,8 @@ uint64_t crc32c_set_small_max(uint64_t n);
 const char *crc32c_strerror(int err);
 
 /* Duration of this thread's last synchronous device batch (milliseconds,
- * hipEvent-measured on its stream); -1 before the first one. */
+ * hipEvent-measured on its stream); -1 before the first one.  After
+ * crc32c_salvage_pages: its scan's counting pass over the eligible bytes. */
 float crc32c_last_kernel_ms(void);
 
 #ifdef __cplusplus

@@ -21,6 +21,7 @@ CRC32C_EINVAL = -3
 CRC32C_ENOMEM = -4
 CRC32C_ERANGE = -5
 CRC32C_EWALK = -6
+CRC32C_EWORK = -7
 
 CRC32C_DEVICE = 0x1
 CRC32C_ASYNC = 0x2
@@ -31,6 +32,7 @@ CRC32C_ITEM_KEPT = 2
 CRC32C_ITEM_COPIED = 1  # ok[] values of crc32c_copy_items
 CRC32C_ITEM_DAMAGED = 3
 CRC32C_MAX_SPAN = 0x7FFF0000  # longest span (include/crc32c_batch.h)
+CRC32C_SALVAGE_WORK_MAX = 64  # crc32c_salvage_pages' work bound: candidates' spans per scanned byte
 
 # every symbol include/*.h declares (checked by tests/test_abi.py)
 EXPORTED = (
@@ -39,7 +41,7 @@ EXPORTED = (
     "crc32c_verify_pages", "crc32c_batch_chains", "crc32c_host_alloc", "crc32c_host_free",
     "crc32c_batch_submit", "crc32c_batch_wait", "crc32c_strerror", "crc32c_last_kernel_ms",
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
-    "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items",
+    "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
 )
 
 
@@ -102,6 +104,12 @@ def _load():
                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                           ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint,
                                           ctypes.c_void_p]
+    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_salvage_pages"):  # (an A/B against an older build)
+        lib.crc32c_salvage_pages.restype = ctypes.c_int
+        lib.crc32c_salvage_pages.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint, ctypes.c_void_p]
     lib.crc32c_batch_chains.restype = ctypes.c_int
     lib.crc32c_batch_chains.argtypes = [ctypes.POINTER(Spans), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                         ctypes.c_uint, ctypes.c_void_p]

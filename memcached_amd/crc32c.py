@@ -11,6 +11,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``stamp_pages``  walk + stamp whole wbufs on the device (no offset list)
 * ``copy_items``   compaction's rescue copy, verified while it copies (storage.c:1004-1006)
 * ``verify_pages`` walk + verify whole pages on the device (storage.c:950-1070)
+* ``salvage_pages`` the intact images behind a header that ended a wbuf's walk
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
 
@@ -28,7 +29,7 @@ from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
-           "copy_items",
+           "copy_items", "salvage_pages",
            "batch_multi",
            "shard_cuts", "queue_stats", "set_small_max", "gpu_count", "Crc32cError"]
 
@@ -358,6 +359,76 @@ def verify_pages(buf, wbuf_bytes, stream=None, cflags64=False):
     n = nitems.value
     assert n <= cap, "item count above the proven bound"
     return offs[:n], ok[:n], int(nbad.value)
+
+
+def salvage_pages(buf, wbuf_bytes, walked=None, walked_ok=None, stream=None, cflags64=False):
+    """The intact images of ``buf`` that the page walk did not reach
+    (crc32c_salvage_pages): every offset outside the walk's good images is
+    tried as an image start, and those whose stored CRC matches are returned.
+
+    ``walked`` / ``walked_ok``: the offsets and flags verify_pages returned for
+    the same buffer (None: nothing is covered, every intact image is found
+    from scratch).  Returns (offsets, {"scanned": eligible offsets, "ncand":
+    those with a sane header and a CRLF}) for numpy and torch buffers, like
+    verify_pages.  When the candidates' spans exceed the work bound the call
+    raises Crc32cError(CRC32C_EWORK) with ``scanned`` and ``ncand`` as
+    attributes of the error."""
+    try:
+        wbuf_bytes = operator.index(wbuf_bytes)
+    except TypeError:
+        wbuf_bytes = 0
+    if wbuf_bytes <= 0:
+        raise ValueError("wbuf_bytes: need a positive integer")
+    if (walked is None) != (walked_ok is None):
+        raise ValueError("walked and walked_ok go together")
+    dev = _is_torch(buf) and buf.is_cuda
+    nfound, scanned, ncand = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    fl = CRC32C_CFLAGS64 if cflags64 else 0
+    if dev:
+        import torch
+        if not buf.is_contiguous():
+            raise ValueError("buf: need a contiguous device tensor")
+        nwalked = 0 if walked is None else walked.numel()
+        if nwalked:
+            _check_dev(walked, "walked", nwalked, ("int64", "uint64"))
+            _check_dev(walked_ok, "walked_ok", nwalked, ("uint8",))
+        if stream is None:
+            stream = torch.cuda.current_stream(buf.device).cuda_stream
+        nbytes = buf.numel() * buf.element_size()
+        fl |= CRC32C_DEVICE
+
+        def alloc(cap):
+            return torch.empty(cap, dtype=torch.int64, device=buf.device)
+    else:
+        buf = _host_buf(buf)
+        nbytes = buf.size
+        nwalked = 0 if walked is None else len(walked)
+        if nwalked:
+            walked = np.ascontiguousarray(walked, dtype=np.uint64)
+            walked_ok = np.ascontiguousarray(walked_ok, dtype=np.uint8)
+            if walked_ok.size != nwalked:
+                raise ValueError(f"walked_ok: {walked_ok.size} flags for {nwalked} offsets")
+        stream = None
+
+        def alloc(cap):
+            return np.empty(cap, np.uint64)
+    # a first guess of the capacity (the images behind the damage of one wbuf
+    # in a hundred, 1 KiB each); a second call with the exact count otherwise
+    cap = nbytes // (100 * 1024) + 64
+    while True:
+        offs = alloc(cap)
+        rc = lib.crc32c_salvage_pages(_ptr(buf), nbytes, wbuf_bytes, _ptr(walked) if nwalked else None,
+                                      _ptr(walked_ok) if nwalked else None, nwalked, _ptr(offs), cap,
+                                      ctypes.byref(nfound), ctypes.byref(scanned), ctypes.byref(ncand), fl, stream)
+        if rc == _lib.CRC32C_EWORK:
+            err = Crc32cError(rc, "crc32c_salvage_pages")
+            err.scanned, err.ncand = int(scanned.value), int(ncand.value)
+            raise err
+        check(rc, "crc32c_salvage_pages")
+        n = nfound.value
+        if n <= cap:
+            return offs[:n], {"scanned": int(scanned.value), "ncand": int(ncand.value)}
+        cap = n
 
 
 def batch_chains(buf, offsets, lens, chain_first, stream=None):

@@ -57,6 +57,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_host.h"
 #include "shim_queue.h"
 #include "shim_walk.h"
+#include "shim_salvage.h"
 
 // Batch C ABI
 extern "C" {
@@ -104,6 +105,7 @@ const char *crc32c_strerror(int err) {
         case CRC32C_ENOMEM: return "out of device or pinned memory";
         case CRC32C_ERANGE: return "span outside [base, base + base_bytes) (not read)";
         case CRC32C_EWALK: return "device page walk passes disagreed (results not valid)";
+        case CRC32C_EWORK: return "salvage candidates' spans exceed the work bound (nothing verified)";
         default: return "unknown error";
     }
 }
@@ -321,6 +323,13 @@ int crc32c_verify_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_byt
                         uint64_t cap, uint64_t *nitems, uint64_t *nbad, unsigned flags, void *stream) {
     return walk_pages<1>(const_cast<void *>(base), base_bytes, wbuf_bytes, offsets, ok, cap, nitems, nbad, flags,
                          stream);
+}
+
+int crc32c_salvage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, const uint64_t *walked,
+                         const uint8_t *walked_ok, uint64_t nwalked, uint64_t *offsets, uint64_t cap,
+                         uint64_t *nfound, uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
+    return salvage_pages(base, base_bytes, wbuf_bytes, walked, walked_ok, nwalked, offsets, cap, nfound, scanned,
+                         ncand, flags, stream);
 }
 
 int crc32c_shard_cuts(const uint32_t *lens, uint32_t len, uint64_t n, int parts, uint64_t *cuts) {

@@ -116,6 +116,15 @@ struct Device {
     DevBuf<uint64_t> fb_offs;
     DevBuf<uint8_t> fb_ok;
     DevBuf<uint2> rt;
+    // crc32c_salvage_pages: staged host lists, the counters and their pinned
+    // twin, the tiles with their candidate counts and scan, the candidates
+    // (offset, ntotal, verdict) and a host call's offsets found
+    DevBuf<uint64_t> sv_walked, sv_cand, sv_out;
+    DevBuf<uint8_t> sv_wok, sv_ok;
+    DevBuf<unsigned long long> sv_ctr;
+    PinBuf<unsigned long long> sv_host;
+    DevBuf<mcrc_dev::SalvageTile> sv_tiles;
+    DevBuf<uint32_t> sv_tcnt, sv_tpre, sv_nt;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

@@ -4,7 +4,8 @@
     python tools/codeobj_diff.py OLD.so NEW.so
 
 Per function symbol: the disassembly (llvm-objdump -d --no-show-raw-insn, the
-trailing `// address` comments stripped).  Per kernel: the VGPR, SGPR and AGPR
+trailing `// address` comments stripped, and the padding between a function's
+last instruction and the next symbol dropped).  Per kernel: the VGPR, SGPR and AGPR
 counts, the LDS, scratch and kernarg sizes, .name and .symbol of its metadata
 note.  Prints the names that differ, or that only one side has, and exits 1 if
 there are any: the gate of a refactor that must not change the device code.
@@ -42,6 +43,16 @@ def functions(co):
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and line.strip():
             cur.append(re.sub(r"\s*//.*$", "", line).strip())
+    # what follows a function's last s_endpgm up to the next symbol is padding
+    # (s_nop fill behind the section's last function, "..." for skipped zeros):
+    # it moves when a function is added behind it and is no instruction of it
+    # (only behind an instruction that ends the function: nothing else is cut)
+    for body in out.values():
+        k = len(body)
+        while k and body[k - 1] in ("s_nop 0", "..."):
+            k -= 1
+        if k and body[k - 1].split()[0] in ("s_endpgm", "s_branch", "s_setpc_b64"):
+            del body[k:]
     return out
 
 
