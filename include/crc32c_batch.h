@@ -107,9 +107,11 @@ extern "C" {
  *   span i = [base + (offsets ? offsets[i] : i * stride),  + (lens ? lens[i] : len))
  *   out[i] = crc32c(crc_in ? crc_in[i] : 0, span i)
  * base_bytes bounds every span: no byte outside [base, base + base_bytes) is
- * read.  A span that does not fit is skipped (out[i] = 0) and the call returns
- * CRC32C_ERANGE (device batches with CRC32C_ASYNC cannot report it: their
- * out-of-range spans still read nothing and get 0).  A batch of equal spans
+ * read.  In a device batch (CRC32C_DEVICE) a span that does not fit is skipped
+ * (out[i] = 0) and the call returns CRC32C_ERANGE (with CRC32C_ASYNC it cannot
+ * report it: the out-of-range spans still read nothing and get 0).  A host
+ * batch with such a span, a job of crc32c_batch_submit included, is refused
+ * whole: CRC32C_EINVAL, nothing read, out untouched.  A batch of equal spans
  * at a fixed stride that overruns base_bytes is rejected up front
  * (CRC32C_EINVAL).  offsets / lens / crc_in / out hold n entries each.
  * Spans may come in any order and may overlap (chunked-item iov lists keep
@@ -164,8 +166,16 @@ int crc32c_verify_items(const void *base, uint64_t base_bytes, uint64_t region_b
  * crc = crc32c(crc, chunk_x, len_x) for every chunk.  iovs describes every
  * iov of every chain (crc_in must be NULL; iovs->out receives each iov's own
  * CRC and must hold iovs->n entries); chain c is iovs [chain_first[c],
- * chain_first[c+1]) (nchains + 1 entries) and out[c] its chained CRC.  All
- * arrays are host or device memory per flags, as for crc32c_batch. */
+ * chain_first[c+1]) (nchains + 1 entries) and out[c] its chained CRC; a chain
+ * of no iovs gets 0.  All arrays are host or device memory per flags, as for
+ * crc32c_batch.  An iov outside the buffer is treated as crc32c_batch treats
+ * the span: a device call skips it (its iovs->out entry is 0, CRC32C_ERANGE)
+ * and the chain that contains it has an unspecified value, every other chain
+ * its exact one; a host call is refused whole (CRC32C_EINVAL).  A host
+ * chain_first that descends or passes iovs->n is refused (CRC32C_EINVAL); a
+ * device chain_first is not validated: it must ascend and stay within
+ * iovs->n, or the fold reads outside the arrays.  nchains == 0: CRC32C_OK,
+ * nothing written. */
 int crc32c_batch_chains(const crc32c_spans *iovs, const uint64_t *chain_first, uint64_t nchains,
                         uint32_t *out, unsigned flags, void *stream);
 

@@ -10,6 +10,9 @@
 //   host_route_check             every assertion; prints the fixed-length K5 and
 //                                k_blocks sets ("k5 <len>..." / "blocks <len>...")
 //   host_route_check cuts PARTS  span lengths on stdin -> crc32c_shard_cuts' cut points
+//   host_route_check route N LEN STRIDE OFFSETS LENS BASE_MOD BASE_BYTES SMALL_MAX
+//                                the name of span_route's answer for that batch
+//                                (OFFSETS / LENS: 1 when the array is given)
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -284,10 +287,27 @@ int print_cuts(int parts) {
     return 0;
 }
 
+// The route of one batch as a test describes it (no array is read).
+int print_route(char **v) {
+    crc32c_spans s{};
+    s.n = strtoull(v[0], nullptr, 0);
+    s.len = (uint32_t)strtoul(v[1], nullptr, 0);
+    s.stride = strtoull(v[2], nullptr, 0);
+    s.offsets = atoi(v[3]) ? kSomeOffsets : nullptr;
+    s.lens = atoi(v[4]) ? kSomeLens : nullptr;
+    s.base = (const void *)(0x7f0000000000ull + strtoull(v[5], nullptr, 0));
+    s.base_bytes = strtoull(v[6], nullptr, 0);
+    static const char *const names[] = {"empty", "invalid", "k1", "small", "k5", "id_blocks", "id_spans",
+                                        "id_final", "planned"};
+    printf("%s\n", names[(int)mcrc::span_route(s, strtoull(v[7], nullptr, 0))]);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc == 3 && !strcmp(argv[1], "cuts")) return print_cuts(atoi(argv[2]));
+    if (argc == 10 && !strcmp(argv[1], "route")) return print_route(argv + 2);
     fixed_length_routes();
     small_rule();
     item_routes();

@@ -59,6 +59,25 @@ def test_scalar_all_lengths():
             assert f(int(g["cin"][n, off]), base + off, n) == g["crcin"][n, off]
 
 
+def test_scalar_lengths_of_the_block_merge():
+    """The built library's `crc32c` data symbol and crc32c_sw at lengths where
+    the hardware path's 3 x 4096-B round runs (from 12 288 bytes behind the
+    alignment prologue; test_scalar_all_lengths stops at 4200): the oracle's
+    CRC at every start 0..7.  (tests/integration/host_crc_check.cpp covers
+    the source at more lengths; this shows the shipped .so carries it.)"""
+    from tests import oracle
+    raw = np.random.default_rng(12288).integers(0, 256, 36871 + 8 + 64, dtype=np.uint8)
+    pad = (-raw.ctypes.data) % 64
+    f = _lib.scalar_crc32c()
+    for n in (12288, 12295, 36871):
+        for off in range(8):
+            view = raw[pad + off:pad + off + n]
+            for cin in (0, 0xdeadbeef):
+                want = oracle.crc32c(cin, view)
+                assert f(cin, view.ctypes.data, n) == want, (n, off, cin)
+                assert _lib.lib.crc32c_sw(cin, view.ctypes.data, n) == want, (n, off, cin)
+
+
 def test_sw_big_matches_the_reference_symbol():
     """crc32c_sw_big (crc32c.c:467-498) equals the reference's own exported
     function on this host (tests/golden/swbig.npz), at every length 0..300,

@@ -45,6 +45,21 @@ def test_host_route_decisions(exe):
     assert blocks == list(range(4081, 4098)) and sets["blocks"] == blocks
 
 
+def test_chain_cases_take_the_routes_they_name(exe):
+    """tests/chain_cases.py labels every case with the span route its iovs take
+    in a device call (the base 16-B aligned, as device allocations are):
+    span_route's own answer for each, so test_gpu_chains.py does run the fold
+    behind K1, K5, k_blocks, k_spans, k_final, k_small and the planned path."""
+    from tests import chain_cases as cc
+    cases = cc.small_cases() + [cc.million_case()]
+    for c in cases:
+        args = [c.n, c.length, c.stride, int(c.offsets is not None), int(c.lens is not None), 0, c.buf.size,
+                8192 if c.small_max is None else c.small_max]
+        r = subprocess.run([exe, "route"] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and r.stdout.strip() == c.route, (c.name, r.stdout, r.stderr)
+    assert {c.route for c in cases} == {"k1", "small", "k5", "id_blocks", "id_spans", "id_final", "planned"}
+
+
 @pytest.mark.parametrize("parts", range(1, 9))
 def test_shard_cuts_match_plan(exe, parts):
     """crc32c_shard_cuts' body against memcached_amd/shard.py plan() on the
