@@ -16,6 +16,25 @@ namespace mcrc_dev {
 // K1 geometry: a 32-lane group owns one 4096-B item, a wave two items per
 // step.
 constexpr uint32_t kK1Bytes = 4096;
+// K1's lockstep rounds: every kK1RoundSteps steps (a multiple of 4: K1's main
+// loop takes 4 steps a pass) the waves of a workgroup meet at a bare
+// workgroup barrier, so that they finish together and the CU keeps its full
+// load depth until its ranges are done.  4, 8, 16 and 32 alternated with the
+// barrier-free loop on one box: 0.6314, 0.6390, 0.6394, 0.6431 against
+// 0.6557 ms per headline launch (profiles/k1_lockstep_ab.jsonl).
+constexpr uint32_t kK1RoundSteps = 4;
+static_assert(kK1RoundSteps >= 4 && kK1RoundSteps % 4 == 0, "a round is whole passes of K1's 4-step loop");
+// Rounds only in launches of at least this many steps per wave (256 Ki items
+// on 256 CUs): the waves' first meeting costs 1-2 us that a short launch has
+// no tail to win back.  Rounds of 4 steps: +2.5-4 % at 8 steps per wave,
+// +1 % at 16, -1.7 % at 32, -3.5 % at 128 and 512 (same file).
+constexpr uint32_t kK1RoundsMinSteps = 32;
+// The barriers every wave of a K1 launch executes, whatever its own range: a
+// function of cg alone (the steps of a full range, the same for every wave of
+// the grid).  A wave arrives once per S steps it runs in its 4-step loop, as
+// long as it owes an arrival (floor(nsteps / S) <= floor(cg / S) times), and
+// makes up the rest after its last store (k_fixed.h).
+MCRC_HD uint64_t k1_rounds(uint64_t cg, uint32_t S) { return cg >= kK1RoundsMinSteps ? cg / S : 0; }
 constexpr uint32_t kRowBytes = 1024;  // a row: two of K1's 512-B piece rows (the head-block skip)
 constexpr uint32_t kBlockBytes = 4 * kRowBytes;  // 4096
 // (round 5: 128 KiB; config 3 -1.1..-1.3 % against 64 KiB in two sessions, the

@@ -29,22 +29,42 @@ __device__ __forceinline__ uint32_t k1_half_value(const K1Half &r, const LaneCtx
     return xor3(x[0], x[1], x[2]) ^ x[3];
 }
 
+// A round's end: a bare workgroup barrier.  It carries no data, so unlike
+// __syncthreads() it has no fence, whose vmcnt(0) would drain the prefetched
+// half-steps; the sched_barriers keep the loads and chains on their sides.
+__device__ __forceinline__ void k1_round_barrier() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// The probe policy of k_fixed_body: points of a wave's life.  The product
+// passes this no-op, which compiles away; tools/k1_timeline.hip passes one
+// that stamps the clocks (its exit() drains the output stores first).
+struct K1NoProbe {
+    __device__ __forceinline__ void steps(uint64_t /*done*/) const {}  // at the bottom of a 4-step pass
+    __device__ __forceinline__ void exit() const {}
+};
+
+// K1's body behind the table copy (k_fixed below is the product's kernel
+// around it).  The copy and the read of blockDim.x (nthreads) stay in the
+// kernel: a function is optimised on its own before it is inlined, and
+// blockDim.x read in here no longer folded to the dispatch packet's field
+// (a select between two loads instead, 9 instructions more per kernel).
 // NT: non-temporal loads, for a 128-B aligned base and stride (every line
 // whole in one item); otherwise the default policy, so that a line two
 // neighbouring items share is not fetched twice (the ldh lambda below).
-template <bool CRCIN, bool NT>
-__global__ __launch_bounds__(1024) void k_fixed(const uint8_t *__restrict__ base, uint64_t stride,
-                                                uint64_t nitems, const uint4 *__restrict__ img,
-                                                const uint32_t *__restrict__ crc_in,
-                                                uint32_t *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    load_tables(smem, img, kLdsImageK1Bytes);
+template <bool CRCIN, bool NT, class Probe>
+__device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, uint64_t stride, uint64_t nitems,
+                                             const uint4 *__restrict__ img, const uint32_t *__restrict__ crc_in,
+                                             uint32_t *__restrict__ out, uint32_t nthreads,
+                                             const Probe &probe) {
     constexpr uint32_t IPW = 2;  // items per wave and step
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t li = lane & 31u;
     const uint32_t g = lane >> 5;
     const LaneCtx c = make_lane_ctx(li);
-    const uint64_t waves = blockDim.x >> 6;
+    const uint64_t waves = nthreads >> 6;
     const uint64_t gstep = gridDim.x * waves;
     const uint64_t ngroups = (nitems + IPW - 1) / IPW;
     // wave-uniform (SGPR) group index: the loop exits are then scalar
@@ -66,7 +86,16 @@ __global__ __launch_bounds__(1024) void k_fixed(const uint8_t *__restrict__ base
     const uint64_t cg = (ngroups + gstep - 1) / gstep;
     const uint64_t gend = min((grp + 1) * cg, ngroups);
     grp *= cg;
-    if (grp >= ngroups) return;
+    // Lockstep rounds: the barriers this wave still owes its workgroup, from
+    // cg alone (k1_rounds, k_consts.h), so every wave of the grid starts with
+    // the same count -- also a wave whose range is empty or cut short at the
+    // batch's end.  It arrives once per kK1RoundSteps steps of its 4-step loop
+    // while it owes an arrival (never in a launch too short for rounds) and
+    // makes up the rest behind its last store: every wave executes exactly
+    // k1_rounds(cg) barriers on every path, and nothing relies on ended waves
+    // being dropped from the barrier.
+    uint64_t owed = k1_rounds(cg, kK1RoundSteps);
+    const bool busy = grp < ngroups;  // (wave-uniform) an empty range only pays its barriers
     const uint64_t glast = gend - 1;
     auto item_of = [&](uint64_t gi) { return gi * IPW + g; };
 
@@ -113,10 +142,6 @@ __global__ __launch_bounds__(1024) void k_fixed(const uint8_t *__restrict__ base
     // Step k's halves live in h0/h1 (k even) or h2/h3 (k odd).  Before step k
     // is checksummed, its two halves and step k + 1's first are issued; each
     // half's checksum is preceded by the issue of the half three later.
-    const uint64_t nsteps = gend - grp;
-    ldh(h0, grp, 0);
-    ldh(h1, grp, 1);
-    ldh(h2, grp + 1, 0);
     // (even step k at grp: h0/h1 -> issue h3 (k+1, B), h0 (k+2, A))
     auto step_even = [&](uint64_t s) {
         ldh(h3, s + 1, 1);
@@ -130,34 +155,58 @@ __global__ __launch_bounds__(1024) void k_fixed(const uint8_t *__restrict__ base
         ldh(h2, s + 2, 0);
         return part0(u0, h3);
     };
-    // One exit, at the bottom of each loop: a break between the halves would
-    // give the loop header a second (un-waited) predecessor, and the waitcnt
-    // pass would then drain every prefetched load there.
-    uint64_t k = 0;
-    for (; k + 4 <= nsteps; k += 4) {
-        const uint32_t va = step_even(grp);
-        const uint32_t vb = step_odd(grp + 1);
-        const uint32_t vab = group_pair_level1(va, vb, lane);
-        const uint32_t vc = step_even(grp + 2);
-        const uint32_t vd = step_odd(grp + 3);
-        const uint32_t raw = group_reduce32_quad_span(vab, group_pair_level1(vc, vd, lane), lane);
-        const uint64_t item = item_of(grp + (li & 3u));
-        if (li < 4 && item < nitems) out[item] = ~raw;
-        grp += 4;
+    if (busy) {
+        const uint64_t nsteps = gend - grp;  // (<= cg)
+        ldh(h0, grp, 0);
+        ldh(h1, grp, 1);
+        ldh(h2, grp + 1, 0);
+        // One exit, at the bottom of each loop: a break between the halves would
+        // give the loop header a second (un-waited) predecessor, and the waitcnt
+        // pass would then drain every prefetched load there.
+        uint64_t k = 0;
+        for (; k + 4 <= nsteps; k += 4) {
+            const uint32_t va = step_even(grp);
+            const uint32_t vb = step_odd(grp + 1);
+            const uint32_t vab = group_pair_level1(va, vb, lane);
+            const uint32_t vc = step_even(grp + 2);
+            const uint32_t vd = step_odd(grp + 3);
+            const uint32_t raw = group_reduce32_quad_span(vab, group_pair_level1(vc, vd, lane), lane);
+            const uint64_t item = item_of(grp + (li & 3u));
+            if (li < 4 && item < nitems) out[item] = ~raw;
+            grp += 4;
+            // (the three half-steps in flight stay in flight across it)
+            if ((k + 4) % kK1RoundSteps == 0 && owed) {
+                k1_round_barrier();
+                --owed;
+            }
+            probe.steps(k + 4);
+        }
+        for (; k + 2 <= nsteps; k += 2) {
+            const uint32_t va = step_even(grp);
+            const uint32_t vb = step_odd(grp + 1);
+            const uint32_t raw = group_reduce32_pair_span(va, vb, lane);
+            const uint64_t item = item_of(li == 0 ? grp : grp + 1);
+            if (li < 2 && item < nitems) out[item] = ~raw;
+            grp += 2;
+        }
+        if (nsteps & 1) {
+            const uint32_t raw = group_reduce32_single_span(step_even(grp), lane);
+            const uint64_t item = item_of(grp);
+            if (li == 0 && item < nitems) out[item] = ~raw;
+        }
     }
-    for (; k + 2 <= nsteps; k += 2) {
-        const uint32_t va = step_even(grp);
-        const uint32_t vb = step_odd(grp + 1);
-        const uint32_t raw = group_reduce32_pair_span(va, vb, lane);
-        const uint64_t item = item_of(li == 0 ? grp : grp + 1);
-        if (li < 2 && item < nitems) out[item] = ~raw;
-        grp += 2;
-    }
-    if (nsteps & 1) {
-        const uint32_t raw = group_reduce32_single_span(step_even(grp), lane);
-        const uint64_t item = item_of(grp);
-        if (li == 0 && item < nitems) out[item] = ~raw;
-    }
+    for (; owed; --owed) k1_round_barrier();
+    probe.exit();
+}
+
+template <bool CRCIN, bool NT>
+__global__ __launch_bounds__(1024) void k_fixed(const uint8_t *__restrict__ base, uint64_t stride,
+                                                uint64_t nitems, const uint4 *__restrict__ img,
+                                                const uint32_t *__restrict__ crc_in,
+                                                uint32_t *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    load_tables(smem, img, kLdsImageK1Bytes);
+    k_fixed_body<CRCIN, NT>(base, stride, nitems, img, crc_in, out, blockDim.x, K1NoProbe{});
 }
 
 }  // namespace mcrc_dev
