@@ -410,6 +410,13 @@ int crc32c_host_unregister(void *p);
  * previous value. */
 uint64_t crc32c_set_small_max(uint64_t n);
 
+/* Tuning, for tests and benchmarks: batches of equal 4 KiB spans whose waves
+ * each run at least `steps` steps (a step: two spans) have their last eighth
+ * claimed in chunks by the waves that finish first; shorter ones are split
+ * evenly.  UINT64_MAX: never; values below the smallest the split supports
+ * (8) count as that.  Process-wide; returns the previous value. */
+uint64_t crc32c_set_k1_tail_min(uint64_t steps);
+
 const char *crc32c_strerror(int err);
 
 /* Duration of this thread's last synchronous device batch (milliseconds,

@@ -42,6 +42,7 @@ EXPORTED = (
     "crc32c_batch_submit", "crc32c_batch_wait", "crc32c_strerror", "crc32c_last_kernel_ms",
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
+    "crc32c_set_k1_tail_min",
 )
 
 
@@ -135,6 +136,9 @@ def _load():
     lib.crc32c_host_unregister.argtypes = [ctypes.c_void_p]
     lib.crc32c_set_small_max.restype = ctypes.c_uint64
     lib.crc32c_set_small_max.argtypes = [ctypes.c_uint64]
+    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_set_k1_tail_min"):  # (an A/B against an older build)
+        lib.crc32c_set_k1_tail_min.restype = ctypes.c_uint64
+        lib.crc32c_set_k1_tail_min.argtypes = [ctypes.c_uint64]
     lib.crc32c_init()
     return lib
 

@@ -31,7 +31,7 @@ from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAM
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
            "batch_multi",
-           "shard_cuts", "queue_stats", "set_small_max", "gpu_count", "Crc32cError"]
+           "shard_cuts", "queue_stats", "set_small_max", "set_k1_tail_min", "gpu_count", "Crc32cError"]
 
 
 def _host_buf(data):
@@ -482,3 +482,9 @@ def queue_stats():
 def set_small_max(n: int) -> int:
     """Batches of at most n spans take the single-launch kernel (0: none); returns the previous value."""
     return int(lib.crc32c_set_small_max(n))
+
+
+def set_k1_tail_min(steps: int) -> int:
+    """Batches of equal 4 KiB spans with at least `steps` steps per wave have their last eighth claimed in
+    chunks (2**64 - 1: never); returns the previous value."""
+    return int(lib.crc32c_set_k1_tail_min(steps))

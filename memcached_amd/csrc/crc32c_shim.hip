@@ -34,6 +34,7 @@
 #include "crc32c_host.h"
 #include "grow_buf.h"
 #include "host_route.h"
+#include "k1_slots.h"
 #include "crc32c_kernels.hip"
 
 // Scalar drop-in (crc32c.h)
@@ -94,6 +95,10 @@ int crc32c_host_unregister(void *p) {
 
 uint64_t crc32c_set_small_max(uint64_t n) {
     return g_small_max.exchange(std::min<uint64_t>(n, mcrc_dev::kSmallMax));
+}
+
+uint64_t crc32c_set_k1_tail_min(uint64_t steps) {
+    return g_k1_tail_min.exchange(std::max<uint64_t>(steps, mcrc_dev::kK1TailFloorSteps));
 }
 
 const char *crc32c_strerror(int err) {

@@ -35,6 +35,72 @@ constexpr uint32_t kK1RoundsMinSteps = 32;
 // long as it owes an arrival (floor(nsteps / S) <= floor(cg / S) times), and
 // makes up the rest after its last store (k_fixed.h).
 MCRC_HD uint64_t k1_rounds(uint64_t cg, uint32_t S) { return cg >= kK1RoundsMinSteps ? cg / S : 0; }
+// K1's claimed tail: the XCDs do not run at one rate, so equal static shares
+// leave the faster ones idle at the end of a launch.  The last 1 / 2^kK1TailShift
+// of every range goes into a pool instead, cut into chunks of kK1TailSteps
+// groups that the waves claim as they finish.  Chunk c belongs to sub-pool
+// c % kK1TailPools (one per wave slot of a workgroup, a counter each), with
+// index c / kK1TailPools in it.  The static part, groups [0, W cg_s), is K1's
+// split of 2 W cg_s items: a full range of cg_s steps for every wave.
+// Libraries alternated with the parent's on one box, ms per launch, medians
+// (profiles/k1_tail_ab.jsonl; the parent's spread over the rounds 0.002 at 1 Mi
+// items, 0.003-0.007 at 4 Mi):
+//   items           parent   1/8, chunks of 4   1/16     1/4      chunks of 2
+//   1 Mi            0.6373   0.6246 (-2.0 %)    +0.6 %   -0.3 %   0.6261 (-1.8 %)
+//   4 Mi            2.5227   2.4646 (-2.3 %)                      2.4634 (-2.3 %, -2.6 % for 4 beside it)
+// (1/16 and 1/4 in a session of their own: against the 1/8 library beside
+// them +2.5 % and +1.6 %.  Chunks of 2: a variant that claims at the top of a
+// chunk for the chunk after next and reads the claim at the chunk's bottom.)
+constexpr uint32_t kK1TailShift = 3;
+constexpr uint32_t kK1TailSteps = 4;  // (K1's 4-step pass: a chunk is one pass)
+constexpr uint32_t kK1TailPools = 16;
+// The smallest cg the split supports: from here on cg_s <= cg - 1, so the
+// static part never reaches past the batch.
+constexpr uint32_t kK1TailFloorSteps = 1u << kK1TailShift;
+static_assert(kK1TailFloorSteps >= 8, "cg_s = 4 must leave a pool");
+// The tail runs in launches of at least this many steps per wave (the default
+// of crc32c_set_k1_tail_min; 320 Ki items on 256 CUs).  Against the parent,
+// same file, the threshold set for the run: +10.5 % at 64 Ki items (8 steps per
+// wave), +3.5 % at 128 Ki (16), +4.8 % at 256 Ki (32: a static part of 28 steps
+// is also too short for the lockstep rounds); at 37 steps, the first static
+// part of 32, -1.4 % in the median but not in every round; -3.4 % at 320 Ki
+// (40), -2.1 % at 384 Ki (48), -1.5 % at 512 Ki (64), -2.0 % at 1 Mi (128),
+// -2.3 % at 4 Mi (512).
+constexpr uint32_t kK1TailMinSteps = 40;
+static_assert(kK1TailMinSteps >= kK1RoundsMinSteps && kK1TailMinSteps >= kK1TailFloorSteps, "");
+struct K1Tail {
+    uint64_t cg_s;     // steps of every wave's static range (a multiple of 4, at least 4)
+    uint64_t pool0;    // the pool's first group, W cg_s
+    uint64_t nchunks;  // chunks of kK1TailSteps groups in [pool0, ngroups), the last one maybe cut
+};
+// (ngroups: pairs of items, the last maybe of one; W: the grid's waves; for
+// ceil(ngroups / W) >= kK1TailFloorSteps)
+MCRC_HD K1Tail k1_tail_split(uint64_t ngroups, uint64_t W) {
+    const uint64_t cg = (ngroups + W - 1) / W;
+    const uint64_t keep = (cg - (cg >> kK1TailShift)) & ~3ull;
+    K1Tail t;
+    t.cg_s = keep < 4 ? 4 : keep;
+    t.pool0 = W * t.cg_s;
+    t.nchunks = (ngroups - t.pool0 + kK1TailSteps - 1) / kK1TailSteps;
+    return t;
+}
+// Chunks of sub-pool t: ceil((nchunks - t) / kK1TailPools), floored at 0.
+MCRC_HD uint64_t k1_tail_pool_chunks(uint64_t nchunks, uint32_t t) {
+    return nchunks > t ? (nchunks - t + kK1TailPools - 1) / kK1TailPools : 0;
+}
+// The counters of one stream's K1 launches (k1_slots.h): a claim head per
+// sub-pool and the count of workgroups done, each on a 256-B line of its own
+// (atomics on one line serialise like atomics on one word).  All zero between
+// launches, kept so by the kernel's last workgroup.
+struct K1Line {
+    uint32_t v;
+    uint32_t pad[63];
+};
+struct K1Ctl {
+    K1Line head[kK1TailPools];
+    K1Line done;
+};
+static_assert(sizeof(K1Line) == 256 && sizeof(K1Ctl) == 256 * (kK1TailPools + 1), "one line per counter");
 constexpr uint32_t kRowBytes = 1024;  // a row: two of K1's 512-B piece rows (the head-block skip)
 constexpr uint32_t kBlockBytes = 4 * kRowBytes;  // 4096
 // (round 5: 128 KiB; config 3 -1.1..-1.3 % against 64 KiB in two sessions, the

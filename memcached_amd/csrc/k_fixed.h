@@ -42,7 +42,9 @@ __device__ __forceinline__ void k1_round_barrier() {
 // passes this no-op, which compiles away; tools/k1_timeline.hip passes one
 // that stamps the clocks (its exit() drains the output stores first).
 struct K1NoProbe {
-    __device__ __forceinline__ void steps(uint64_t /*done*/) const {}  // at the bottom of a 4-step pass
+    // at the bottom of a 4-step pass: the steps the wave has run, its claimed
+    // chunks included (a cut chunk counts as a whole pass)
+    __device__ __forceinline__ void steps(uint64_t /*done*/) const {}
     __device__ __forceinline__ void exit() const {}
 };
 
@@ -54,10 +56,13 @@ struct K1NoProbe {
 // NT: non-temporal loads, for a 128-B aligned base and stride (every line
 // whole in one item); otherwise the default policy, so that a line two
 // neighbouring items share is not fetched twice (the ldh lambda below).
+// ctl: null, or the launch's counters (K1Ctl, k_consts.h): the launch then
+// runs k1_tail_split's static part in the loop below and claims the pool's
+// chunks behind it ("The claimed tail").
 template <bool CRCIN, bool NT, class Probe>
 __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, uint64_t stride, uint64_t nitems,
                                              const uint4 *__restrict__ img, const uint32_t *__restrict__ crc_in,
-                                             uint32_t *__restrict__ out, uint32_t nthreads,
+                                             uint32_t *__restrict__ out, uint32_t nthreads, K1Ctl *__restrict__ ctl,
                                              const Probe &probe) {
     constexpr uint32_t IPW = 2;  // items per wave and step
     const uint32_t lane = threadIdx.x & 63u;
@@ -83,8 +88,11 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     // boxes (profiles/r04_ablations/k1_chunk_and_census_ab.txt,
     // k1_item_order_ab.txt); a range per workgroup with its waves interleaved
     // was 4.5 % slower
-    const uint64_t cg = (ngroups + gstep - 1) / gstep;
-    const uint64_t gend = min((grp + 1) * cg, ngroups);
+    // (with a claimed tail: the static part's full ranges of cg_s steps)
+    const bool tail = ctl != nullptr;  // (a kernel argument: wave-uniform)
+    const K1Tail tl = tail ? k1_tail_split(ngroups, gstep) : K1Tail{0, 0, 0};
+    const uint64_t cg = tail ? tl.cg_s : (ngroups + gstep - 1) / gstep;
+    uint64_t gend = min((grp + 1) * cg, ngroups);
     grp *= cg;
     // Lockstep rounds: the barriers this wave still owes its workgroup, from
     // cg alone (k1_rounds, k_consts.h), so every wave of the grid starts with
@@ -96,7 +104,7 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     // being dropped from the barrier.
     uint64_t owed = k1_rounds(cg, kK1RoundSteps);
     const bool busy = grp < ngroups;  // (wave-uniform) an empty range only pays its barriers
-    const uint64_t glast = gend - 1;
+    uint64_t glast = gend - 1;
     auto item_of = [&](uint64_t gi) { return gi * IPW + g; };
 
     // The loads run three half-steps ahead: a ring of four half-buffers (the
@@ -142,21 +150,33 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     // Step k's halves live in h0/h1 (k even) or h2/h3 (k odd).  Before step k
     // is checksummed, its two halves and step k + 1's first are issued; each
     // half's checksum is preceded by the issue of the half three later.
-    // (even step k at grp: h0/h1 -> issue h3 (k+1, B), h0 (k+2, A))
-    auto step_even = [&](uint64_t s) {
-        ldh(h3, s + 1, 1);
+    // (even step k at grp: h0/h1 -> issue h3 (k+1, B), h0 (k+2, A)); a and b
+    // are the groups of steps k + 1 and k + 2: s + 1 and s + 2 inside a range
+    auto step_even2 = [&](uint64_t a, uint64_t b) {
+        ldh(h3, a, 1);
         const uint32_t u0 = half0(h0);
-        ldh(h0, s + 2, 0);
+        ldh(h0, b, 0);
         return part0(u0, h1);
     };
-    auto step_odd = [&](uint64_t s) {
-        ldh(h1, s + 1, 1);
+    auto step_odd2 = [&](uint64_t a, uint64_t b) {
+        ldh(h1, a, 1);
         const uint32_t u0 = half0(h2);
-        ldh(h2, s + 2, 0);
+        ldh(h2, b, 0);
         return part0(u0, h3);
     };
+    auto step_even = [&](uint64_t s) { return step_even2(s + 1, s + 2); };
+    auto step_odd = [&](uint64_t s) { return step_odd2(s + 1, s + 2); };
+    // the stores of a 4-step pass over the groups first .. first + 3
+    auto store4 = [&](uint32_t vab, uint32_t vc, uint32_t vd, uint64_t first) {
+        const uint32_t raw = group_reduce32_quad_span(vab, group_pair_level1(vc, vd, lane), lane);
+        const uint64_t item = item_of(first + (li & 3u));
+        if (li < 4 && item < nitems) out[item] = ~raw;
+    };
+    uint64_t ran = 0;  // steps run (for the probe)
     if (busy) {
-        const uint64_t nsteps = gend - grp;  // (<= cg)
+        // (<= cg; with a claimed tail the range's last pass is left to the
+        // tail loop, whose first chunk it is)
+        const uint64_t nsteps = gend - grp - (tail ? 4u : 0u);
         ldh(h0, grp, 0);
         ldh(h1, grp, 1);
         ldh(h2, grp + 1, 0);
@@ -170,9 +190,7 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
             const uint32_t vab = group_pair_level1(va, vb, lane);
             const uint32_t vc = step_even(grp + 2);
             const uint32_t vd = step_odd(grp + 3);
-            const uint32_t raw = group_reduce32_quad_span(vab, group_pair_level1(vc, vd, lane), lane);
-            const uint64_t item = item_of(grp + (li & 3u));
-            if (li < 4 && item < nitems) out[item] = ~raw;
+            store4(vab, vc, vd, grp);
             grp += 4;
             // (the three half-steps in flight stay in flight across it)
             if ((k + 4) % kK1RoundSteps == 0 && owed) {
@@ -181,6 +199,7 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
             }
             probe.steps(k + 4);
         }
+        ran = k;
         for (; k + 2 <= nsteps; k += 2) {
             const uint32_t va = step_even(grp);
             const uint32_t vb = step_odd(grp + 1);
@@ -195,18 +214,77 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
             if (li == 0 && item < nitems) out[item] = ~raw;
         }
     }
+    // (with a claimed tail: the arrival of the pass left to the tail loop, one
+    // pass early for every wave of the workgroup alike)
     for (; owed; --owed) k1_round_barrier();
+    // The claimed tail.  Every range here is full and a multiple of 4 steps, so
+    // the loop above left grp at the range's last pass with that pass's first
+    // three half-steps in flight: the pass is this loop's first chunk.  Wave
+    // slot t claims index i of sub-pool t with one relaxed agent-scope add
+    // (lane 0's, a returning vector atomic) at the top of a chunk and runs
+    // chunk 16 i + t behind it: the claim comes back while two steps are
+    // checksummed, and the chunk's last two steps prefetch the claimed
+    // chunk's first half-steps, so the ring of four stays full across chunks.
+    // A failed claim (i >= the sub-pool's chunks) prefetches the table image,
+    // as a range's end does, and ends the loop: every wave makes exactly one.
+    // No barrier in here and nothing waits for another wave.  The pool's last
+    // chunk may be cut: its missing groups load the table image and their
+    // items lie past nitems, so the stores' guard drops them.
+    if (tail) {
+        const uint32_t t = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const uint64_t mine = k1_tail_pool_chunks(tl.nchunks, t);
+        gend = ngroups;
+        glast = ngroups - 1;
+        // (the head's address through a VGPR the compiler cannot see through:
+        // for a wave-uniform address its atomic optimiser rewrites the add as
+        // a wave reduction, whose readfirstlane sits right behind the atomic
+        // and waits for it with vmcnt(0), draining the ring)
+        typedef __attribute__((address_space(1))) uint32_t gu32;
+        gu32 *head = (gu32 *)&ctl->head[t].v;
+        asm volatile("" : "+v"(head));
+        uint64_t cur = grp, nxt;
+        do {
+            uint32_t i = 0;
+            if (lane == 0) i = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t va = step_even(cur);
+            const uint32_t vb = step_odd(cur + 1);
+            const uint32_t vab = group_pair_level1(va, vb, lane);
+            i = __builtin_amdgcn_readfirstlane(i);
+            // (ngroups: no chunk; it and ngroups + 1 load the table image)
+            nxt = i < mine ? tl.pool0 + ((uint64_t)i * kK1TailPools + t) * kK1TailSteps : ngroups;
+            const uint32_t vc = step_even2(cur + 3, nxt);
+            const uint32_t vd = step_odd2(nxt, nxt + 1);
+            store4(vab, vc, vd, cur);
+            cur = nxt;
+            ran += 4;
+            probe.steps(ran);
+        } while (nxt < ngroups);
+        // The launch's end: one more bare barrier for every wave, behind which
+        // every claim of the workgroup has returned (each was waited for above).
+        // The last workgroup to count itself done then zeroes the counters for
+        // the stream's next launch; no claim can follow it.
+        k1_round_barrier();
+        if (threadIdx.x < 64) {
+            uint32_t old = 0;
+            if (lane == 0) old = __hip_atomic_fetch_add(&ctl->done.v, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((uint32_t)__builtin_amdgcn_readfirstlane(old) == gridDim.x - 1 && lane <= kK1TailPools)
+                __hip_atomic_store(lane < kK1TailPools ? &ctl->head[lane].v : &ctl->done.v, 0u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
     probe.exit();
 }
 
+// ctl: null for today's static K1, else the counters of this stream's launches
+// (launch_k1, shim_launch.h).
 template <bool CRCIN, bool NT>
 __global__ __launch_bounds__(1024) void k_fixed(const uint8_t *__restrict__ base, uint64_t stride,
                                                 uint64_t nitems, const uint4 *__restrict__ img,
                                                 const uint32_t *__restrict__ crc_in,
-                                                uint32_t *__restrict__ out) {
+                                                uint32_t *__restrict__ out, K1Ctl *__restrict__ ctl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     load_tables(smem, img, kLdsImageK1Bytes);
-    k_fixed_body<CRCIN, NT>(base, stride, nitems, img, crc_in, out, blockDim.x, K1NoProbe{});
+    k_fixed_body<CRCIN, NT>(base, stride, nitems, img, crc_in, out, blockDim.x, ctl, K1NoProbe{});
 }
 
 }  // namespace mcrc_dev

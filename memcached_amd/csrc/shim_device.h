@@ -56,6 +56,11 @@ struct Device {
     // images): zero between calls, kept so by the kernel's last workgroup
     unsigned long long *small_nbad = nullptr;
     uint32_t *small_done = nullptr;  // ([1]: k_copy's count of images that did not fit dst, kept the same way)
+    // K1's claimed tail: a counter block per stream (k1_slots.h), zero between
+    // launches, kept so by the kernel's last workgroup; the table is the one
+    // piece of state a launch (const Device &, no mu) writes
+    mcrc_dev::K1Ctl *k1_ctl = nullptr;
+    mutable mcrc::K1Slots k1_slots;
     uint32_t *nfb = nullptr;    // k_lines' fallback count (device)
     uint32_t *route = nullptr;  // k_census's verdict: K5 (1) or the planned path (0)
     hipStream_t stream = nullptr, copy = nullptr;
@@ -238,6 +243,8 @@ int init_device(Device &d, int id) {
     HIP_OK(hipMalloc(&d.small_nbad, 16));
     HIP_OK(hipMemset(d.small_nbad, 0, 16));
     d.small_done = reinterpret_cast<uint32_t *>(d.small_nbad + 1);
+    HIP_OK(hipMalloc(&d.k1_ctl, mcrc::kK1Slots * sizeof(mcrc_dev::K1Ctl)));
+    HIP_OK(hipMemset(d.k1_ctl, 0, mcrc::kK1Slots * sizeof(mcrc_dev::K1Ctl)));
     HIP_OK(hipMalloc(&d.nfb, 2 * sizeof(uint32_t)));
     d.route = d.nfb + 1;
     for (hipStream_t *s : {&d.stream, &d.copy, &d.side}) HIP_OK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
@@ -258,6 +265,7 @@ int init_device(Device &d, int id) {
     };
     for (const void *k : k160)
         HIP_OK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mcrc_dev::kLdsImageK1Bytes));
+    HIP_OK(hipDeviceSynchronize());  // (the memsets above, before a launch on a non-blocking stream)
     d.ok = true;
     return CRC32C_OK;
 }

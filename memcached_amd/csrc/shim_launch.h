@@ -9,6 +9,7 @@ thread_local float g_last_kernel_ms = -1.0f;
 
 std::atomic<uint64_t> g_small_max{mcrc_dev::kSmallMax};  // crc32c_set_small_max
 uint64_t small_max() { return g_small_max.load(std::memory_order_relaxed); }
+std::atomic<uint64_t> g_k1_tail_min{mcrc_dev::kK1TailMinSteps};  // crc32c_set_k1_tail_min
 
 int ensure_plan(Device &d, uint64_t n, uint64_t cap) {
     const uint64_t ntiles = mcrc::plan_tiles(n);
@@ -63,13 +64,32 @@ mcrc_dev::SpanArgs item_args(const Device &d, const void *base, uint64_t base_by
     return a;
 }
 
+// The counters of a K1 launch of n items on st, or null: the launch is then
+// split evenly.  Null below the tail's threshold, for a stream without a slot
+// (k1_slots.h) and for a capturing stream: a replayed graph may run twice at
+// once, on one slot.
+mcrc_dev::K1Ctl *k1_ctl(const Device &d, uint64_t n, hipStream_t st) {
+    const uint64_t waves = (uint64_t)mcrc::grid_for(d.cus, n) * (1024 / 64);
+    const uint64_t cg = ((n + 1) / 2 + waves - 1) / waves;
+    if (cg < g_k1_tail_min.load(std::memory_order_relaxed)) return nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    if (cap != hipStreamCaptureStatusNone) return nullptr;
+    const int slot = d.k1_slots.find((void *)st, (void *)hipStreamLegacy, (void *)hipStreamPerThread);
+    return slot < 0 ? nullptr : d.k1_ctl + slot;
+}
+
 // K1.  Non-temporal loads only when every 128-B line belongs to one item.
 int launch_k1(const Device &d, const crc32c_spans &s, hipStream_t st) {
     const bool nt = ((uintptr_t)s.base & 127u) == 0 && (s.stride & 127u) == 0;
+    mcrc_dev::K1Ctl *ctl = k1_ctl(d, s.n, st);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(mcrc::grid_for(d.cus, s.n)), dim3(1024), mcrc_dev::kLdsImageK1Bytes, st,
                            (const uint8_t *)s.base, s.stride, s.n, (const uint4 *)d.img, (const uint32_t *)s.crc_in,
-                           s.out);
+                           s.out, ctl);
     };
     if (s.crc_in) nt ? go(mcrc_dev::k_fixed<true, true>) : go(mcrc_dev::k_fixed<true, false>);
     else nt ? go(mcrc_dev::k_fixed<false, true>) : go(mcrc_dev::k_fixed<false, false>);

@@ -3,8 +3,10 @@
 // (k_fixed_body, k_fixed.h) with a probe that stamps, per wave, the constant
 // 100 MHz counter and the shader-clock counter at entry, after the table copy,
 // every 8 steps and at exit (after the output stores have drained), plus the
-// wave's XCC id and hardware id.  Lane 0 writes the stamps with plain vector
-// stores.  The stamped launch's CRCs are checked equal to the product
+// wave's XCC id and hardware id and the steps it ran (its claimed chunks
+// included).  Both kernels get a counter block (K1Ctl) when the launch is long
+// enough for the claimed tail; K1_TAIL=0 in the environment runs them without.
+// Lane 0 writes the stamps with plain vector stores.  The stamped launch's CRCs are checked equal to the product
 // kernel's on the same batch.  Printed per item count:
 //   - the product's and the stamped kernel's event times (what the stamps cost)
 //   - wave, workgroup and XCD end percentiles (laid out like
@@ -44,22 +46,24 @@ constexpr uint64_t kItemBytes = 4096, kStepBytes = 2 * kItemBytes;
 constexpr uint32_t kEvery = 8;  // a stamp every 8 steps
 
 // A wave's row: slot 0 entry, 1 after the table copy, 2 exit, 3 {hw id, xcc
-// id}, 4 + j after step 8 (j + 1).
+// id}, 4 {steps run, 0}, 5 + j after step 8 (j + 1).
 struct Stamp {
     uint64_t rt, sc;  // 100 MHz ticks, shader-clock ticks
 };
-constexpr uint32_t kFixedSlots = 4;
+constexpr uint32_t kFixedSlots = 5;
 
 struct StampProbe {
     Stamp *row;
     uint32_t slots;  // of the row: nothing is written past it
     uint32_t lane;
+    mutable uint64_t ran = 0;
     __device__ __forceinline__ void mark(uint32_t slot) const {
         const uint64_t rt = __builtin_amdgcn_s_memrealtime();
         const uint64_t sc = __builtin_amdgcn_s_memtime();
         if (lane == 0 && slot < slots) row[slot] = Stamp{rt, sc};
     }
     __device__ __forceinline__ void steps(uint64_t done) const {
+        ran = done;
         if (done % kEvery == 0) mark(kFixedSlots + (uint32_t)(done / kEvery) - 1);
     }
     __device__ __forceinline__ void exit() const {
@@ -67,20 +71,21 @@ struct StampProbe {
         mark(2);
         const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_ID
         const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-        if (lane == 0 && 3 < slots) row[3] = Stamp{hw, xcc};
+        if (lane == 0 && 4 < slots) row[3] = Stamp{hw, xcc}, row[4] = Stamp{ran, 0};
     }
 };
 
 __global__ __launch_bounds__(1024) void k_fixed_stamped(const uint8_t *__restrict__ base, uint64_t stride,
                                                         uint64_t nitems, const uint4 *__restrict__ img,
-                                                        uint32_t *__restrict__ out, Stamp *st, uint32_t slots) {
+                                                        uint32_t *__restrict__ out, K1Ctl *__restrict__ ctl, Stamp *st,
+                                                        uint32_t slots) {
     const uint32_t wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const StampProbe probe{st + (uint64_t)wid * slots, slots, threadIdx.x & 63u};
     probe.mark(0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     load_tables(smem, img, kLdsImageK1Bytes);
     probe.mark(1);
-    k_fixed_body<false, true>(base, stride, nitems, img, nullptr, out, blockDim.x, probe);
+    k_fixed_body<false, true>(base, stride, nitems, img, nullptr, out, blockDim.x, ctl, probe);
 }
 
 __global__ void fill(uint32_t *p, uint64_t n) {
@@ -125,7 +130,7 @@ struct Wave {
     double t_entry, t_tables, t_end;  // us since the first entry
 };
 
-static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t slots) {
+static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t slots, bool claimed) {
     const uint64_t nw = (uint64_t)grid * 16, ngroups = (n + 1) / 2, cg = (ngroups + nw - 1) / nw;
     uint64_t t0 = ~0ull;
     for (uint64_t w = 0; w < nw; ++w) t0 = std::min(t0, st[w * slots].rt);
@@ -139,10 +144,11 @@ static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t
         x.xcc = (uint32_t)r[3].sc & 15u;
         uint64_t grp = nw % 65521u ? (w * 65521u) % nw : w;  // K1's range split (k_fixed.h)
         const uint64_t g0 = grp * cg, g1 = std::min((grp + 1) * cg, ngroups);
-        x.nsteps = g0 < ngroups ? g1 - g0 : 0;
+        // (with the claimed tail: what the wave counted, whole passes)
+        x.nsteps = claimed ? r[4].rt : g0 < ngroups ? g1 - g0 : 0;
         x.t_entry = us(r[0].rt), x.t_tables = us(r[1].rt), x.t_end = us(r[2].rt);
         x.s.push_back(r[1]), x.done.push_back(0);
-        for (uint64_t d = kEvery; d <= x.nsteps / 4 * 4; d += kEvery)
+        for (uint64_t d = kEvery; d <= x.nsteps / 4 * 4 && kFixedSlots + d / kEvery - 1 < slots; d += kEvery)
             x.s.push_back(r[kFixedSlots + d / kEvery - 1]), x.done.push_back(d);
         x.s.push_back(r[2]), x.done.push_back(x.nsteps);
         span = std::max(span, x.t_end);
@@ -154,6 +160,23 @@ static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t
     std::vector<double> e, b, c, ends;
     for (auto &x : wv) e.push_back(x.t_entry), c.push_back(x.t_tables - x.t_entry), ends.push_back(x.t_end);
     e = sorted(e), c = sorted(c), ends = sorted(ends);
+    if (claimed) {
+        std::vector<double> ns;
+        for (auto &x : wv) ns.push_back((double)x.nsteps);
+        ns = sorted(ns);
+        const K1Tail tl = k1_tail_split(ngroups, nw);
+        printf("\nn %llu: claimed tail: %llu static steps per wave, %llu chunks of %u steps; steps run per wave p0/p10/p50/p90/p100 "
+               "%.0f/%.0f/%.0f/%.0f/%.0f",
+               (unsigned long long)n, (unsigned long long)tl.cg_s, (unsigned long long)tl.nchunks, (unsigned)kK1TailSteps,
+               ns.front(), pct(ns, 10), pct(ns, 50), pct(ns, 90), ns.back());
+        for (uint32_t xc = 0; xc < 16; ++xc) {
+            double sum = 0;
+            size_t cnt = 0;
+            for (auto &x : wv)
+                if (x.xcc == xc) sum += (double)x.nsteps, ++cnt;
+            if (cnt) printf("%s xcc %u %.1f", xc ? "," : "; mean per XCD:", xc, sum / cnt);
+        }
+    }
     printf("\nn %llu: span %.1f us; grid %d x 16 waves, %llu steps per wave; wave start p0/p50/p100 %.1f/%.1f/%.1f us; "
            "table copy p50/p100 %.1f/%.1f us\n",
            (unsigned long long)n, span, grid, (unsigned long long)cg, e.front(), pct(e, 50), e.back(), pct(c, 50),
@@ -264,7 +287,14 @@ int main(int argc, char **argv) {
     hipDeviceProp_t p;
     CHECK(hipGetDeviceProperties(&p, 0));
     const int cus = p.multiProcessorCount;
-    printf("device %s  CUs %d  K1 lockstep round: %u steps\n", p.gcnArchName, cus, (unsigned)kK1RoundSteps);
+    const bool want_tail = !(getenv("K1_TAIL") && atoi(getenv("K1_TAIL")) == 0);
+    printf("device %s  CUs %d  K1 lockstep round: %u steps; claimed tail %s (from %u steps per wave, 1/%u of a range, chunks of "
+           "%u steps)\n",
+           p.gcnArchName, cus, (unsigned)kK1RoundSteps, want_tail ? "on" : "off", (unsigned)kK1TailMinSteps,
+           1u << kK1TailShift, (unsigned)kK1TailSteps);
+    K1Ctl *dctl;
+    CHECK(hipMalloc(&dctl, sizeof(K1Ctl)));
+    CHECK(hipMemset(dctl, 0, sizeof(K1Ctl)));
     const uint64_t nmax = *std::max_element(sizes.begin(), sizes.end());
     uint8_t *d;
     uint32_t *out, *out_ref;
@@ -284,17 +314,20 @@ int main(int argc, char **argv) {
     for (uint64_t n : sizes) {
         const int grid = mcrc::grid_for(cus, n);
         const uint64_t nw = (uint64_t)grid * 16, cg = ((n + 1) / 2 + nw - 1) / nw;
-        const uint32_t slots = kFixedSlots + (uint32_t)(cg / kEvery) + 1;
+        // (a wave that claims runs more steps than cg: rows of twice that, and
+        // nothing is written past a row)
+        const uint32_t slots = kFixedSlots + (uint32_t)(2 * cg / kEvery) + 1;
+        K1Ctl *ctl = want_tail && cg >= kK1TailMinSteps ? dctl : nullptr;
         Stamp *st;
         CHECK(hipMalloc(&st, nw * slots * sizeof(Stamp)));
         CHECK(hipMemset(st, 0, nw * slots * sizeof(Stamp)));
         auto product = [&] {
             hipLaunchKernelGGL((k_fixed<false, true>), dim3(grid), dim3(1024), kLdsImageK1Bytes, 0, d, kItemBytes, n, dimg,
-                               nullptr, out_ref);
+                               nullptr, out_ref, ctl);
         };
         auto stamped = [&] {
-            hipLaunchKernelGGL(k_fixed_stamped, dim3(grid), dim3(1024), kLdsImageK1Bytes, 0, d, kItemBytes, n, dimg, out, st,
-                               slots);
+            hipLaunchKernelGGL(k_fixed_stamped, dim3(grid), dim3(1024), kLdsImageK1Bytes, 0, d, kItemBytes, n, dimg, out, ctl,
+                               st, slots);
         };
         // clock settle: 300 ms of back-to-back product launches
         const auto c0 = std::chrono::steady_clock::now();
@@ -320,7 +353,7 @@ int main(int argc, char **argv) {
         printf("n %llu: stamped CRCs %s the product kernel's\n", (unsigned long long)n, same ? "equal" : "DIFFER FROM");
         std::vector<Stamp> hs(nw * slots);
         CHECK(hipMemcpy(hs.data(), st, hs.size() * sizeof(Stamp), hipMemcpyDeviceToHost));  // (the last stamped launch)
-        analyse(n, grid, hs, slots);
+        analyse(n, grid, hs, slots, ctl != nullptr);
         fflush(stdout);
         CHECK(hipFree(st));
         if (!same) return 1;
