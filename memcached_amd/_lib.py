@@ -67,78 +67,56 @@ class Spans(ctypes.Structure):
     ]
 
 
+_INT, _UINT, _U32, _U64 = ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, ctypes.c_uint64
+_SIZE, _PTR, _SPANS, _U64P = ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(Spans), ctypes.POINTER(ctypes.c_uint64)
+_SCALAR = (_U32, [_U32, _PTR, _SIZE])  # crc_func of include/crc32c.h
+_ITEMS = (_INT, [_PTR, _U64, _U64, _PTR, _U64, _PTR, _U64P, _UINT, _PTR])
+_PAGES = (_INT, [_PTR, _U64, _U64, _PTR, _PTR, _U64, _U64P, _U64P, _UINT, _PTR])
+
+# name -> (restype, argtypes) of every function in EXPORTED, as include/*.h declares them
+PROTOTYPES = {
+    "crc32c_init": (None, []),
+    "crc32c_sw": _SCALAR,
+    "crc32c_sw_little": _SCALAR,
+    "crc32c_sw_big": _SCALAR,
+    "crc32c_gpu_count": (_INT, []),
+    "crc32c_batch": (_INT, [_SPANS, _UINT, _PTR]),
+    "crc32c_batch_multi": (_INT, [_SPANS, _INT]),
+    "crc32c_verify_items": _ITEMS,
+    "crc32c_stamp_items": _ITEMS,
+    "crc32c_verify_pages": _PAGES,
+    "crc32c_stamp_pages": _PAGES,
+    "crc32c_copy_items": (_INT, [_PTR, _U64, _U64, _PTR, _PTR, _U64, _PTR, _U64, _PTR, _U64P, _UINT, _PTR]),
+    "crc32c_salvage_pages": (_INT, [_PTR, _U64, _U64, _PTR, _PTR, _U64, _PTR, _U64, _U64P, _U64P, _U64P, _UINT,
+                                    _PTR]),
+    "crc32c_batch_chains": (_INT, [_SPANS, _PTR, _U64, _PTR, _UINT, _PTR]),
+    "crc32c_host_alloc": (_PTR, [_SIZE]),
+    "crc32c_host_free": (None, [_PTR]),
+    "crc32c_batch_submit": (_INT, [_SPANS, _UINT, ctypes.POINTER(_PTR)]),
+    "crc32c_batch_wait": (_INT, [_PTR]),
+    "crc32c_strerror": (ctypes.c_char_p, [_INT]),
+    "crc32c_last_kernel_ms": (ctypes.c_float, []),
+    "crc32c_shard_cuts": (_INT, [_PTR, _U32, _U64, _INT, _PTR]),
+    "crc32c_queue_stats": (_INT, [_U64P] * 4),
+    "crc32c_host_register": (_INT, [_PTR, _SIZE]),
+    "crc32c_host_unregister": (_INT, [_PTR]),
+    "crc32c_set_small_max": (_U64, [_U64]),
+    "crc32c_set_k1_tail_min": (_U64, [_U64]),
+}
+# what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
+NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min")
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: run `python -m memcached_amd.build`")
     # the HIP runtime already loaded by torch (same soname) is reused when present
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    lib.crc32c_init.restype = None
-    lib.crc32c_init.argtypes = []
-    for name in ("crc32c_sw", "crc32c_sw_little"):
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if name in NEWER and os.environ.get("MCRC_LIB") and not hasattr(lib, name):
+            continue
         f = getattr(lib, name)
-        f.restype = ctypes.c_uint32
-        f.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
-    lib.crc32c_gpu_count.restype = ctypes.c_int
-    lib.crc32c_batch.restype = ctypes.c_int
-    lib.crc32c_batch.argtypes = [ctypes.POINTER(Spans), ctypes.c_uint, ctypes.c_void_p]
-    lib.crc32c_batch_multi.restype = ctypes.c_int
-    lib.crc32c_batch_multi.argtypes = [ctypes.POINTER(Spans), ctypes.c_int]
-    lib.crc32c_verify_items.restype = ctypes.c_int
-    lib.crc32c_verify_items.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                        ctypes.c_uint64,
-                                        ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint,
-                                        ctypes.c_void_p]
-    lib.crc32c_stamp_items.restype = ctypes.c_int
-    lib.crc32c_stamp_items.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                       ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
-                                       ctypes.c_uint, ctypes.c_void_p]
-    lib.crc32c_verify_pages.restype = ctypes.c_int
-    lib.crc32c_verify_pages.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
-                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint, ctypes.c_void_p]
-    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_stamp_pages"):  # (an A/B against an older build)
-        lib.crc32c_stamp_pages.restype = ctypes.c_int
-        lib.crc32c_stamp_pages.argtypes = lib.crc32c_verify_pages.argtypes
-    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_copy_items"):  # (an A/B against an older build)
-        lib.crc32c_copy_items.restype = ctypes.c_int
-        lib.crc32c_copy_items.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint,
-                                          ctypes.c_void_p]
-    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_salvage_pages"):  # (an A/B against an older build)
-        lib.crc32c_salvage_pages.restype = ctypes.c_int
-        lib.crc32c_salvage_pages.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
-                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint, ctypes.c_void_p]
-    lib.crc32c_batch_chains.restype = ctypes.c_int
-    lib.crc32c_batch_chains.argtypes = [ctypes.POINTER(Spans), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                        ctypes.c_uint, ctypes.c_void_p]
-    lib.crc32c_host_alloc.restype = ctypes.c_void_p
-    lib.crc32c_host_alloc.argtypes = [ctypes.c_size_t]
-    lib.crc32c_host_free.restype = None
-    lib.crc32c_host_free.argtypes = [ctypes.c_void_p]
-    lib.crc32c_batch_submit.restype = ctypes.c_int
-    lib.crc32c_batch_submit.argtypes = [ctypes.POINTER(Spans), ctypes.c_uint, ctypes.POINTER(ctypes.c_void_p)]
-    lib.crc32c_batch_wait.restype = ctypes.c_int
-    lib.crc32c_batch_wait.argtypes = [ctypes.c_void_p]
-    lib.crc32c_strerror.restype = ctypes.c_char_p
-    lib.crc32c_strerror.argtypes = [ctypes.c_int]
-    lib.crc32c_last_kernel_ms.restype = ctypes.c_float
-    lib.crc32c_shard_cuts.restype = ctypes.c_int
-    lib.crc32c_shard_cuts.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int,
-                                      ctypes.c_void_p]
-    lib.crc32c_queue_stats.restype = ctypes.c_int
-    lib.crc32c_queue_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * 4
-    lib.crc32c_host_register.restype = ctypes.c_int
-    lib.crc32c_host_register.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    lib.crc32c_host_unregister.restype = ctypes.c_int
-    lib.crc32c_host_unregister.argtypes = [ctypes.c_void_p]
-    lib.crc32c_set_small_max.restype = ctypes.c_uint64
-    lib.crc32c_set_small_max.argtypes = [ctypes.c_uint64]
-    if not os.environ.get("MCRC_LIB") or hasattr(lib, "crc32c_set_k1_tail_min"):  # (an A/B against an older build)
-        lib.crc32c_set_k1_tail_min.restype = ctypes.c_uint64
-        lib.crc32c_set_k1_tail_min.argtypes = [ctypes.c_uint64]
+        f.restype, f.argtypes = restype, argtypes
     lib.crc32c_init()
     return lib
 

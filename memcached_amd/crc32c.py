@@ -16,7 +16,9 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``batch_multi``  host batch split across GPUs by bytes
 
 Host inputs are numpy arrays (or bytes); device inputs are torch tensors on a
-HIP device, enqueued on torch's current stream.
+HIP device, enqueued on ``stream`` or else on torch's current stream of that
+device.  Each batch wrapper chooses its side once from the buffer (_side) and
+then reads: marshal, call, check, slice.
 """
 from __future__ import annotations
 
@@ -61,6 +63,10 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+def _is_dev(x) -> bool:
+    return _is_torch(x) and x.is_cuda
+
+
 def _ptr(x):
     if x is None:
         return None
@@ -69,17 +75,153 @@ def _ptr(x):
     return x.ctypes.data
 
 
-def _check_dev(t, name, n, dtypes):
-    """A device descriptor array: contiguous, on the device, one of `dtypes`
-    (names), at least n elements (the kernels read n of them unchecked)."""
-    import torch
-    if not (_is_torch(t) and t.is_cuda and t.is_contiguous()):
-        raise ValueError(f"{name}: device batches need a contiguous device tensor")
-    if str(t.dtype).replace("torch.", "") not in dtypes:
-        raise TypeError(f"{name}: dtype {t.dtype} (need one of {', '.join(dtypes)})")
-    if t.numel() < n:
-        raise ValueError(f"{name}: {t.numel()} elements for {n} spans")
-    return torch
+def _count(x) -> int:
+    return x.numel() if _is_torch(x) else x.size
+
+
+# Element kinds of the descriptor and result arrays: (numpy dtype on the host,
+# dtype names a device tensor may have -- a new one gets the first).
+_U8 = (np.uint8, ("uint8",))
+_U32 = (np.uint32, ("int32", "uint32"))
+_U64 = (np.uint64, ("int64", "uint64"))
+_WRITABLE = "a writable contiguous uint8 numpy array"
+
+
+class _Host:
+    """The host side of a call: numpy arrays, no flag, no stream."""
+    dev, flag, stream = False, 0, None
+
+    def buffer(self, buf, name="buf", inplace=None):
+        """(array, bytes) of a data buffer.  ``inplace``: the call writes it,
+        so nothing is converted; the text of the refusal, {} = _WRITABLE."""
+        if not inplace:
+            buf = _host_buf(buf)
+        elif not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8 and buf.flags.writeable
+                  and buf.flags.c_contiguous):
+            raise TypeError(inplace.format(_WRITABLE))
+        return buf, buf.size
+
+    def desc(self, a, name, kind, n=0, exact=False):
+        """A descriptor array the library reads n elements of, converted to
+        its width (None stays None).  ``exact``: a longer one is refused too."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=kind[0])
+        if a.size < n or (exact and a.size != n):
+            raise ValueError(f"{name}: {a.size} elements for {n} spans")
+        return a
+
+    def out(self, a, name, kind, n):
+        """The caller's result array, checked and never converted, or a new one."""
+        if a is None:
+            return self.empty(n, kind)
+        if a.size < n:
+            raise ValueError(f"{name}: {a.size} elements for {n} spans")
+        if a.dtype.name not in kind[1] or not a.flags.c_contiguous:
+            raise TypeError(f"{name}: need a contiguous {kind[0].__name__} array")
+        return a
+
+    def empty(self, n, kind):
+        return np.empty(n, kind[0])
+
+
+class _Device:
+    """The device side: torch tensors of the buffer's device, CRC32C_DEVICE,
+    the caller's stream or else torch's current stream of that device."""
+    dev, flag = True, CRC32C_DEVICE
+
+    def __init__(self, buf, stream):
+        import torch
+        self.torch, self.device = torch, buf.device
+        self.stream = torch.cuda.current_stream(buf.device).cuda_stream if stream is None else stream
+
+    def buffer(self, buf, name="buf", inplace=None):
+        if not buf.is_contiguous():
+            raise ValueError(f"{name}: need a contiguous device tensor")
+        return buf, buf.numel() * buf.element_size()
+
+    def desc(self, t, name, kind, n=0, exact=False):
+        """Contiguous, on the device, one of the kind's dtypes, at least n
+        elements (the kernels read n of them unchecked; a longer tensor is
+        never refused here, ``exact`` is the host's)."""
+        if t is None:
+            return None
+        if not (_is_dev(t) and t.is_contiguous()):
+            raise ValueError(f"{name}: device batches need a contiguous device tensor")
+        if str(t.dtype).replace("torch.", "") not in kind[1]:
+            raise TypeError(f"{name}: dtype {t.dtype} (need one of {', '.join(kind[1])})")
+        if t.numel() < n:
+            raise ValueError(f"{name}: {t.numel()} elements for {n} spans")
+        return t
+
+    def out(self, t, name, kind, n):
+        return self.empty(n, kind) if t is None else self.desc(t, name, kind, n)
+
+    def empty(self, n, kind):
+        return self.torch.empty(n, dtype=getattr(self.torch, kind[1][0]), device=self.device)
+
+
+_HOST = _Host()
+
+
+def _side(buf, stream=None):
+    """Where a call's data lives, chosen from its buffer."""
+    return _Device(buf, stream) if _is_dev(buf) else _HOST
+
+
+def _flags(cflags64, keep_stamped=False):
+    return (CRC32C_CFLAGS64 if cflags64 else 0) | (CRC32C_KEEP_STAMPED if keep_stamped else 0)
+
+
+def _wbuf_bytes(wbuf_bytes) -> int:
+    try:
+        wbuf_bytes = operator.index(wbuf_bytes)
+    except TypeError:
+        wbuf_bytes = 0
+    if wbuf_bytes <= 0:
+        raise ValueError("wbuf_bytes: need a positive integer")
+    return wbuf_bytes
+
+
+def _check_carrying(rc, what, carrier, **attrs):
+    """check(), but status ``carrier`` comes with partial results: they travel
+    as attributes of the error."""
+    if rc == carrier:
+        err = Crc32cError(rc, what)
+        vars(err).update(attrs)
+        raise err
+    check(rc, what)
+
+
+def _sized(side, kinds, cap, call, proven=False):
+    """Result arrays of the count that ``call(cap, *pointers)`` returns: one
+    call when the results fit ``cap``, else a second one with the exact count.
+    ``proven``: cap is an upper bound, more is a bug."""
+    while True:
+        arrays = [side.empty(cap, kind) for kind in kinds]
+        n = call(cap, *map(_ptr, arrays))
+        if n <= cap:
+            return [a[:n] for a in arrays]
+        assert not proven, "item count above the proven bound"
+        cap = n
+
+
+def _spans(side, buf, offsets, stride, lens, length, crc_in, out):
+    """(crc32c_spans, out) of a batch."""
+    if offsets is not None:
+        n = len(offsets)
+    elif lens is not None:
+        n = len(lens)
+    else:
+        raise ValueError("need offsets or lens to know the batch size")
+    buf, nbytes = side.buffer(buf)
+    offsets = side.desc(offsets, "offsets", _U64, n)
+    lens = side.desc(lens, "lens", _U32, n)
+    crc_in = side.desc(crc_in, "crc_in", _U32, n)
+    out = side.out(out, "out", _U32, n)
+    s = _lib.Spans(_ptr(buf), nbytes, _ptr(offsets), stride, _ptr(lens), length, _ptr(crc_in), _ptr(out), n)
+    s.arrays = buf, offsets, lens, crc_in  # the struct holds bare addresses: converted copies live as long as it does
+    return s, out
 
 
 def batch(buf, offsets=None, stride: int = 0, lens=None, length: int = 0, crc_in=None, out=None,
@@ -97,62 +239,31 @@ def batch(buf, offsets=None, stride: int = 0, lens=None, length: int = 0, crc_in
         import warnings
         warnings.warn("batch(aligned16=...) is ignored (alignment is detected per batch)", DeprecationWarning,
                       stacklevel=2)
-    dev = _is_torch(buf) and buf.is_cuda
-    if offsets is not None:
-        n = len(offsets)
-    elif lens is not None:
-        n = len(lens)
-    else:
-        raise ValueError("need offsets or lens to know the batch size")
-    if dev:
-        import torch
-        if not buf.is_contiguous():
-            raise ValueError("buf: device batches need a contiguous device tensor")
-        if out is None:
-            out = torch.empty(n, dtype=torch.int32, device=buf.device)
-        _check_dev(out, "out", n, ("int32", "uint32"))
-        if offsets is not None:
-            _check_dev(offsets, "offsets", n, ("int64", "uint64"))
-        for name, t in (("lens", lens), ("crc_in", crc_in)):
-            if t is not None:
-                _check_dev(t, name, n, ("int32", "uint32"))
-        base_bytes = buf.numel() * buf.element_size()
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-    else:
-        buf = _host_buf(buf)
-        base_bytes = buf.size
-        offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-        lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
-        crc_in = None if crc_in is None else np.ascontiguousarray(crc_in, dtype=np.uint32)
-        if out is None:
-            out = np.empty(n, dtype=np.uint32)
-        for name, a in (("lens", lens), ("crc_in", crc_in), ("out", out)):
-            if a is not None and a.size < n:
-                raise ValueError(f"{name}: {a.size} elements for {n} spans")
-        if out.dtype not in (np.uint32, np.int32) or not out.flags.c_contiguous:
-            raise TypeError("out: need a contiguous uint32 array")
-    s = _lib.Spans(_ptr(buf), base_bytes, _ptr(offsets), stride, _ptr(lens), length, _ptr(crc_in),
-                   _ptr(out), n)
-    flags = CRC32C_DEVICE if dev else 0
-    if dev and asynchronous:
-        flags |= CRC32C_ASYNC
-    check(lib.crc32c_batch(ctypes.byref(s), flags, stream if dev else None), "crc32c_batch")
+    side = _side(buf, stream)
+    s, out = _spans(side, buf, offsets, stride, lens, length, crc_in, out)
+    flags = side.flag | (CRC32C_ASYNC if side.dev and asynchronous else 0)
+    check(lib.crc32c_batch(ctypes.byref(s), flags, side.stream), "crc32c_batch")
     return out
 
 
 def batch_multi(buf, offsets=None, stride: int = 0, lens=None, length: int = 0, crc_in=None, ngpus: int = 0):
     """Host batch split across ``ngpus`` devices (0 = all) by bytes."""
-    buf = _host_buf(buf)
-    offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-    lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
-    crc_in = None if crc_in is None else np.ascontiguousarray(crc_in, dtype=np.uint32)
-    n = len(offsets) if offsets is not None else len(lens)
-    out = np.empty(n, dtype=np.uint32)
-    s = _lib.Spans(_ptr(buf), buf.size, _ptr(offsets), stride, _ptr(lens), length, _ptr(crc_in),
-                   _ptr(out), n)
+    s, out = _spans(_HOST, buf, offsets, stride, lens, length, crc_in, None)
     check(lib.crc32c_batch_multi(ctypes.byref(s), ngpus), "crc32c_batch_multi")
     return out
+
+
+def _items(what, buf, item_offsets, region_bytes, stream, flags, inplace=None):
+    """crc32c_verify_items / crc32c_stamp_items: (ok, nbad)."""
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf, inplace=inplace)
+    offs = side.desc(item_offsets, "item_offsets", _U64)
+    n = _count(offs)
+    ok = side.empty(n, _U8)
+    nbad = ctypes.c_uint64(0)
+    check(getattr(lib, what)(_ptr(buf), nbytes, region_bytes, _ptr(offs), n, _ptr(ok), ctypes.byref(nbad),
+                             side.flag | flags, side.stream), what)
+    return ok, int(nbad.value)
 
 
 def verify_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False):
@@ -162,27 +273,7 @@ def verify_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False)
     span crossing a multiple of it is reported bad without being read
     (extstore never splits an item across wbufs).  0 = no such bound.
     ``cflags64``: images of a LARGE_CLIENT_FLAGS build (8-byte client flags)."""
-    dev = _is_torch(buf) and buf.is_cuda
-    nbad = ctypes.c_uint64(0)
-    fl = CRC32C_CFLAGS64 if cflags64 else 0
-    if dev:
-        import torch
-        n = item_offsets.numel()
-        _check_dev(item_offsets, "item_offsets", n, ("int64", "uint64"))
-        ok = torch.empty(n, dtype=torch.uint8, device=buf.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-        rc = lib.crc32c_verify_items(buf.data_ptr(), buf.numel() * buf.element_size(), region_bytes,
-                                     item_offsets.data_ptr(), n, ok.data_ptr(), ctypes.byref(nbad),
-                                     CRC32C_DEVICE | fl, stream)
-    else:
-        buf = _host_buf(buf)
-        offs = np.ascontiguousarray(item_offsets, dtype=np.uint64)
-        ok = np.empty(offs.size, dtype=np.uint8)
-        rc = lib.crc32c_verify_items(buf.ctypes.data, buf.size, region_bytes, offs.ctypes.data, offs.size,
-                                     ok.ctypes.data, ctypes.byref(nbad), fl, None)
-    check(rc, "crc32c_verify_items")
-    return ok, int(nbad.value)
+    return _items("crc32c_verify_items", buf, item_offsets, region_bytes, stream, _flags(cflags64))
 
 
 def stamp_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False, keep_stamped=False):
@@ -194,29 +285,8 @@ def stamp_items(buf, item_offsets, region_bytes=0, stream=None, cflags64=False, 
     carries its CRC already (compaction copies images with it); it is verified
     against that value and never written: ok = 2 when it matches, else 0 and
     counted in nbad."""
-    dev = _is_torch(buf) and buf.is_cuda
-    nbad = ctypes.c_uint64(0)
-    fl = (CRC32C_CFLAGS64 if cflags64 else 0) | (CRC32C_KEEP_STAMPED if keep_stamped else 0)
-    if dev:
-        import torch
-        n = item_offsets.numel()
-        _check_dev(item_offsets, "item_offsets", n, ("int64", "uint64"))
-        ok = torch.empty(n, dtype=torch.uint8, device=buf.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-        rc = lib.crc32c_stamp_items(buf.data_ptr(), buf.numel() * buf.element_size(), region_bytes,
-                                    item_offsets.data_ptr(), n, ok.data_ptr(), ctypes.byref(nbad),
-                                    CRC32C_DEVICE | fl, stream)
-    else:
-        if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8 and buf.flags.writeable
-                and buf.flags.c_contiguous):
-            raise TypeError("stamp_items needs a writable contiguous uint8 numpy array (stamped in place)")
-        offs = np.ascontiguousarray(item_offsets, dtype=np.uint64)
-        ok = np.empty(offs.size, dtype=np.uint8)
-        rc = lib.crc32c_stamp_items(buf.ctypes.data, buf.size, region_bytes, offs.ctypes.data, offs.size,
-                                    ok.ctypes.data, ctypes.byref(nbad), fl, None)
-    check(rc, "crc32c_stamp_items")
-    return ok, int(nbad.value)
+    return _items("crc32c_stamp_items", buf, item_offsets, region_bytes, stream, _flags(cflags64, keep_stamped),
+                  inplace="stamp_items needs {} (stamped in place)")
 
 
 def copy_items(src, src_offsets, dst, dst_offsets, region_bytes=0, stream=None, cflags64=False):
@@ -233,44 +303,44 @@ def copy_items(src, src_offsets, dst, dst_offsets, region_bytes=0, stream=None, 
     current stream) or both host buffers, ``dst`` a writable contiguous uint8
     numpy array; ``region_bytes`` and ``cflags64`` apply to the source, as for
     verify_items."""
-    dev = _is_torch(src) and src.is_cuda
-    if dev != (_is_torch(dst) and dst.is_cuda):
+    side = _side(src, stream)
+    if side.dev != _is_dev(dst):
         raise ValueError("copy_items: src and dst must both be device tensors or both be host buffers")
+    dst, dst_bytes = side.buffer(dst, "dst", inplace="copy_items needs {} as dst (written in place)")
+    src, src_bytes = side.buffer(src, "src")
+    soffs = side.desc(src_offsets, "src_offsets", _U64)
+    n = _count(soffs)
+    doffs = side.desc(dst_offsets, "dst_offsets", _U64, n, exact=True)
+    ok = side.empty(n, _U8)
     nbad = ctypes.c_uint64(0)
-    fl = CRC32C_CFLAGS64 if cflags64 else 0
-    if dev:
-        import torch
-        if not (src.is_contiguous() and dst.is_contiguous()):
-            raise ValueError("copy_items: need contiguous device tensors")
-        n = src_offsets.numel()
-        _check_dev(src_offsets, "src_offsets", n, ("int64", "uint64"))
-        _check_dev(dst_offsets, "dst_offsets", n, ("int64", "uint64"))
-        ok = torch.empty(n, dtype=torch.uint8, device=src.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-        rc = lib.crc32c_copy_items(src.data_ptr(), src.numel() * src.element_size(), region_bytes,
-                                   src_offsets.data_ptr(), dst.data_ptr(), dst.numel() * dst.element_size(),
-                                   dst_offsets.data_ptr(), n, ok.data_ptr(), ctypes.byref(nbad), CRC32C_DEVICE | fl,
-                                   stream)
-    else:
-        if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.writeable
-                and dst.flags.c_contiguous):
-            raise TypeError("copy_items needs a writable contiguous uint8 numpy array as dst (written in place)")
-        src = _host_buf(src)
-        soffs = np.ascontiguousarray(src_offsets, dtype=np.uint64)
-        doffs = np.ascontiguousarray(dst_offsets, dtype=np.uint64)
-        if doffs.size != soffs.size:
-            raise ValueError(f"dst_offsets: {doffs.size} elements for {soffs.size} images")
-        ok = np.empty(soffs.size, dtype=np.uint8)
-        rc = lib.crc32c_copy_items(src.ctypes.data, src.size, region_bytes, soffs.ctypes.data, dst.ctypes.data,
-                                   dst.size, doffs.ctypes.data, soffs.size, ok.ctypes.data, ctypes.byref(nbad), fl,
-                                   None)
-    if rc == _lib.CRC32C_ERANGE:  # everything that fits is copied: the verdicts travel with the error
-        err = Crc32cError(rc, "crc32c_copy_items")
-        err.ok, err.nbad = ok, int(nbad.value)
-        raise err
-    check(rc, "crc32c_copy_items")
+    rc = lib.crc32c_copy_items(_ptr(src), src_bytes, region_bytes, _ptr(soffs), _ptr(dst), dst_bytes, _ptr(doffs), n,
+                               _ptr(ok), ctypes.byref(nbad), side.flag | _flags(cflags64), side.stream)
+    # everything that fits is copied: the verdicts travel with the error
+    _check_carrying(rc, "crc32c_copy_items", _lib.CRC32C_ERANGE, ok=ok, nbad=int(nbad.value))
     return ok, int(nbad.value)
+
+
+def _walk_bound(nbytes, wbuf_bytes):
+    """No walk counts more: an image is >= 50 bytes and each wbuf's last
+    counted image may run past its end."""
+    return nbytes // 50 + -(-nbytes // wbuf_bytes)
+
+
+def _pages(what, side, buf, nbytes, wbuf_bytes, flags, cap, proven):
+    """crc32c_verify_pages / crc32c_stamp_pages with result arrays of ``cap``
+    items (_sized): (item offsets, ok flags, nbad) in walk order.  ``cap``
+    None: the count-only query, no arrays; returns the walk's item count."""
+    nitems, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def walk(cap, offs, ok):
+        check(getattr(lib, what)(_ptr(buf), nbytes, wbuf_bytes, offs, ok, cap, ctypes.byref(nitems),
+                                 ctypes.byref(nbad), side.flag | flags, side.stream), what)
+        return nitems.value
+
+    if cap is None:  # count only
+        return walk(0, None, None)
+    offs, ok = _sized(side, (_U64, _U8), cap, walk, proven)
+    return offs, ok, int(nbad.value)
 
 
 def stamp_pages(buf, wbuf_bytes, keep_stamped=False, stream=None, cflags64=False):
@@ -281,84 +351,29 @@ def stamp_pages(buf, wbuf_bytes, keep_stamped=False, stream=None, cflags64=False
     An open wbuf whose tail is not zeroed yet is passed as a slice of the
     bytes used.  Device buffers are walked once more beforehand (a count-only
     crc32c_verify_pages query) to size the result tensors exactly."""
-    try:
-        wbuf_bytes = operator.index(wbuf_bytes)
-    except TypeError:
-        wbuf_bytes = 0
-    if wbuf_bytes <= 0:
-        raise ValueError("wbuf_bytes: need a positive integer")
-    dev = _is_torch(buf) and buf.is_cuda
-    nitems, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    fl = (CRC32C_CFLAGS64 if cflags64 else 0) | (CRC32C_KEEP_STAMPED if keep_stamped else 0)
-    if dev:
-        import torch
-        if not buf.is_contiguous():
-            raise ValueError("buf: need a contiguous device tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-        nbytes = buf.numel() * buf.element_size()
-        check(lib.crc32c_verify_pages(buf.data_ptr(), nbytes, wbuf_bytes, None, None, 0, ctypes.byref(nitems),
-                                      ctypes.byref(nbad), CRC32C_DEVICE | fl, stream), "crc32c_verify_pages")
-        cap = nitems.value
-        offs = torch.empty(cap, dtype=torch.int64, device=buf.device)
-        ok = torch.empty(cap, dtype=torch.uint8, device=buf.device)
-        check(lib.crc32c_stamp_pages(buf.data_ptr(), nbytes, wbuf_bytes, offs.data_ptr(), ok.data_ptr(), cap,
-                                     ctypes.byref(nitems), ctypes.byref(nbad), CRC32C_DEVICE | fl, stream),
-              "crc32c_stamp_pages")
-    else:
-        if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8 and buf.flags.writeable
-                and buf.flags.c_contiguous):
-            raise TypeError("stamp_pages needs a writable contiguous uint8 numpy array (stamped in place)")
-        # an image is >= 50 bytes and each wbuf's last counted image may run past its end
-        cap = buf.size // 50 + -(-buf.size // wbuf_bytes)
-        offs = np.empty(cap, np.uint64)
-        ok = np.empty(cap, np.uint8)
-        check(lib.crc32c_stamp_pages(buf.ctypes.data, buf.size, wbuf_bytes, offs.ctypes.data, ok.ctypes.data, cap,
-                                     ctypes.byref(nitems), ctypes.byref(nbad), fl, None), "crc32c_stamp_pages")
-    n = nitems.value
-    assert n <= cap, "item count above the proven bound"
-    return offs[:n], ok[:n], int(nbad.value)
+    wbuf_bytes = _wbuf_bytes(wbuf_bytes)
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf, inplace="stamp_pages needs {} (stamped in place)")
+    args = side, buf, nbytes, wbuf_bytes, _flags(cflags64, keep_stamped)
+    cap = _pages("crc32c_verify_pages", *args, None, False) if side.dev else _walk_bound(nbytes, wbuf_bytes)
+    return _pages("crc32c_stamp_pages", *args, cap, True)
 
 
 def verify_pages(buf, wbuf_bytes, stream=None, cflags64=False):
     """Walk every wbuf-sized read of ``buf`` on the device and verify each
     item found.  Returns (item offsets, ok flags, nbad) in walk order.
 
-    One library call when the items fit a first guess of the capacity
-    (images of >= 1 KiB on average); otherwise a second call with the exact
-    count the first one reported."""
-    dev = _is_torch(buf) and buf.is_cuda
-    nitems, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    fl = CRC32C_CFLAGS64 if cflags64 else 0
-    if dev:
-        import torch
-        if not buf.is_contiguous():
-            raise ValueError("buf: need a contiguous device tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-        nbytes = buf.numel() * buf.element_size()
-        nw = -(-nbytes // wbuf_bytes)
-        cap = min(nbytes // 1024 + nw, nbytes // 50 + nw)
-        while True:
-            offs = torch.empty(cap, dtype=torch.int64, device=buf.device)
-            ok = torch.empty(cap, dtype=torch.uint8, device=buf.device)
-            check(lib.crc32c_verify_pages(buf.data_ptr(), nbytes, wbuf_bytes, offs.data_ptr(), ok.data_ptr(), cap,
-                                          ctypes.byref(nitems), ctypes.byref(nbad), CRC32C_DEVICE | fl, stream),
-                  "crc32c_verify_pages")
-            n = nitems.value
-            if n <= cap:
-                return offs[:n], ok[:n], int(nbad.value)
-            cap = n
-    buf = _host_buf(buf)
-    # an image is >= 50 bytes and each wbuf's last counted image may run past its end
-    cap = buf.size // 50 + -(-buf.size // wbuf_bytes)
-    offs = np.empty(cap, np.uint64)
-    ok = np.empty(cap, np.uint8)
-    check(lib.crc32c_verify_pages(buf.ctypes.data, buf.size, wbuf_bytes, offs.ctypes.data, ok.ctypes.data, cap,
-                                  ctypes.byref(nitems), ctypes.byref(nbad), fl, None), "crc32c_verify_pages")
-    n = nitems.value
-    assert n <= cap, "item count above the proven bound"
-    return offs[:n], ok[:n], int(nbad.value)
+    Device buffers take one library call when the items fit a first guess of
+    the capacity (images of >= 1 KiB on average), otherwise a second call with
+    the exact count the first one reported.  A host call stages the whole
+    buffer, so there the capacity is the walk's upper bound at once."""
+    wbuf_bytes = _wbuf_bytes(wbuf_bytes)
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf)
+    cap = _walk_bound(nbytes, wbuf_bytes)
+    if side.dev:
+        cap = min(nbytes // 1024 + -(-nbytes // wbuf_bytes), cap)
+    return _pages("crc32c_verify_pages", side, buf, nbytes, wbuf_bytes, _flags(cflags64), cap, not side.dev)
 
 
 def salvage_pages(buf, wbuf_bytes, walked=None, walked_ok=None, stream=None, cflags64=False):
@@ -373,93 +388,42 @@ def salvage_pages(buf, wbuf_bytes, walked=None, walked_ok=None, stream=None, cfl
     verify_pages.  When the candidates' spans exceed the work bound the call
     raises Crc32cError(CRC32C_EWORK) with ``scanned`` and ``ncand`` as
     attributes of the error."""
-    try:
-        wbuf_bytes = operator.index(wbuf_bytes)
-    except TypeError:
-        wbuf_bytes = 0
-    if wbuf_bytes <= 0:
-        raise ValueError("wbuf_bytes: need a positive integer")
+    wbuf_bytes = _wbuf_bytes(wbuf_bytes)
     if (walked is None) != (walked_ok is None):
         raise ValueError("walked and walked_ok go together")
-    dev = _is_torch(buf) and buf.is_cuda
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf)
+    nwalked = 0 if walked is None else len(walked)
+    if not nwalked:
+        walked = walked_ok = None
+    walked = side.desc(walked, "walked", _U64, nwalked)
+    walked_ok = side.desc(walked_ok, "walked_ok", _U8, nwalked, exact=True)
     nfound, scanned, ncand = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-    fl = CRC32C_CFLAGS64 if cflags64 else 0
-    if dev:
-        import torch
-        if not buf.is_contiguous():
-            raise ValueError("buf: need a contiguous device tensor")
-        nwalked = 0 if walked is None else walked.numel()
-        if nwalked:
-            _check_dev(walked, "walked", nwalked, ("int64", "uint64"))
-            _check_dev(walked_ok, "walked_ok", nwalked, ("uint8",))
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-        nbytes = buf.numel() * buf.element_size()
-        fl |= CRC32C_DEVICE
 
-        def alloc(cap):
-            return torch.empty(cap, dtype=torch.int64, device=buf.device)
-    else:
-        buf = _host_buf(buf)
-        nbytes = buf.size
-        nwalked = 0 if walked is None else len(walked)
-        if nwalked:
-            walked = np.ascontiguousarray(walked, dtype=np.uint64)
-            walked_ok = np.ascontiguousarray(walked_ok, dtype=np.uint8)
-            if walked_ok.size != nwalked:
-                raise ValueError(f"walked_ok: {walked_ok.size} flags for {nwalked} offsets")
-        stream = None
+    def scan(cap, offs):
+        rc = lib.crc32c_salvage_pages(_ptr(buf), nbytes, wbuf_bytes, _ptr(walked), _ptr(walked_ok), nwalked, offs, cap,
+                                      ctypes.byref(nfound), ctypes.byref(scanned), ctypes.byref(ncand),
+                                      side.flag | _flags(cflags64), side.stream)
+        _check_carrying(rc, "crc32c_salvage_pages", _lib.CRC32C_EWORK, scanned=int(scanned.value),
+                        ncand=int(ncand.value))
+        return nfound.value
 
-        def alloc(cap):
-            return np.empty(cap, np.uint64)
-    # a first guess of the capacity (the images behind the damage of one wbuf
-    # in a hundred, 1 KiB each); a second call with the exact count otherwise
-    cap = nbytes // (100 * 1024) + 64
-    while True:
-        offs = alloc(cap)
-        rc = lib.crc32c_salvage_pages(_ptr(buf), nbytes, wbuf_bytes, _ptr(walked) if nwalked else None,
-                                      _ptr(walked_ok) if nwalked else None, nwalked, _ptr(offs), cap,
-                                      ctypes.byref(nfound), ctypes.byref(scanned), ctypes.byref(ncand), fl, stream)
-        if rc == _lib.CRC32C_EWORK:
-            err = Crc32cError(rc, "crc32c_salvage_pages")
-            err.scanned, err.ncand = int(scanned.value), int(ncand.value)
-            raise err
-        check(rc, "crc32c_salvage_pages")
-        n = nfound.value
-        if n <= cap:
-            return offs[:n], {"scanned": int(scanned.value), "ncand": int(ncand.value)}
-        cap = n
+    # a first guess of the capacity: the images behind the damage of one wbuf in a hundred, 1 KiB each
+    offs, = _sized(side, (_U64,), nbytes // (100 * 1024) + 64, scan)
+    return offs, {"scanned": int(scanned.value), "ncand": int(ncand.value)}
 
 
 def batch_chains(buf, offsets, lens, chain_first, stream=None):
     """Chained CRC per iov list: chain c covers iovs [chain_first[c],
     chain_first[c+1]) of the spans (offsets[i], lens[i]) of ``buf`` and gets
     crc32c(...crc32c(crc32c(0, iov_a), iov_a+1)..., iov_b-1)."""
-    dev = _is_torch(buf) and buf.is_cuda
-    n, nchains = len(offsets), len(chain_first) - 1
-    if dev:
-        import torch
-        if not buf.is_contiguous():
-            raise ValueError("buf: need a contiguous device tensor")
-        _check_dev(offsets, "offsets", n, ("int64", "uint64"))
-        _check_dev(lens, "lens", n, ("int32", "uint32"))
-        _check_dev(chain_first, "chain_first", nchains + 1, ("int64", "uint64"))
-        iov_out = torch.empty(n, dtype=torch.int32, device=buf.device)
-        out = torch.empty(nchains, dtype=torch.int32, device=buf.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(buf.device).cuda_stream
-        base_bytes = buf.numel() * buf.element_size()
-    else:
-        buf = _host_buf(buf)
-        base_bytes = buf.size
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        chain_first = np.ascontiguousarray(chain_first, dtype=np.uint64)
-        iov_out = np.empty(n, dtype=np.uint32)
-        out = np.empty(nchains, dtype=np.uint32)
-    s = _lib.Spans(_ptr(buf), base_bytes, _ptr(offsets), 0, _ptr(lens), 0, None, _ptr(iov_out), n)
-    check(lib.crc32c_batch_chains(ctypes.byref(s), _ptr(chain_first), nchains, _ptr(out),
-                                  CRC32C_DEVICE if dev else 0, stream if dev else None), "crc32c_batch_chains")
+    side = _side(buf, stream)
+    nchains = len(chain_first) - 1
+    s, _iov_out = _spans(side, buf, offsets, 0, lens, 0, None, None)
+    chain_first = side.desc(chain_first, "chain_first", _U64, nchains + 1)
+    out = side.empty(nchains, _U32)
+    check(lib.crc32c_batch_chains(ctypes.byref(s), _ptr(chain_first), nchains, _ptr(out), side.flag, side.stream),
+          "crc32c_batch_chains")
     return out
 
 

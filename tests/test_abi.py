@@ -35,6 +35,16 @@ def test_every_declared_symbol_is_exported():
     assert declared <= set(_lib.EXPORTED)
 
 
+def test_every_exported_function_has_a_prototype():
+    """_lib.PROTOTYPES covers EXPORTED but the data symbol, and is what the
+    loaded functions carry."""
+    assert set(_lib.PROTOTYPES) == set(_lib.EXPORTED) - {"crc32c"}
+    assert len(set(_lib.EXPORTED)) == len(_lib.EXPORTED)
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        f = getattr(_lib.lib, name)
+        assert f.restype == restype and list(f.argtypes) == argtypes, name
+
+
 def test_crc_func_is_a_data_symbol_set_by_init():
     ptr = ctypes.c_void_p.in_dll(_lib.lib, "crc32c")
     assert ptr.value  # _lib.load() ran crc32c_init()
@@ -84,8 +94,6 @@ def test_sw_big_matches_the_reference_symbol():
     five long lengths and every 8-byte alignment, with and without crc_in."""
     g = np.load(os.path.join(GOLD, "swbig.npz"))
     f = _lib.lib.crc32c_sw_big
-    f.restype = ctypes.c_uint32
-    f.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
     raw = g["buf"].tobytes()
     buf = ctypes.create_string_buffer(raw, len(raw))
     base = ctypes.addressof(buf)
