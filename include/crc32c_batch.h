@@ -24,6 +24,10 @@
  *                          (storage.c:950-1072 loses them silently): every
  *                          unreached offset tried as an image start, the ones
  *                          whose stored CRC proves them reported.
+ *   crc32c_recover_pages   crc32c_verify_pages and crc32c_salvage_pages in one call:
+ *                          the page staged once, the walk's lists kept on the
+ *                          device, one merged list with each image's kind and
+ *                          ITEM_ntotal for a single rescue loop.
  *   crc32c_verify_items    the read-verify compare of storage.c:159-178 applied
  *                          to every item image of a packed extstore page
  *                          (walk of storage.c:950-960): CRC over
@@ -68,7 +72,8 @@ extern "C" {
 #define CRC32C_EWALK (-6)  /* crc32c_verify_pages / _stamp_pages: the device walk's count and emit
                               passes disagreed on some wbuf (an internal invariant;
                               the results are not valid) */
-#define CRC32C_EWORK (-7)  /* crc32c_salvage_pages: the candidates' spans exceed the work bound */
+#define CRC32C_EWORK (-7)  /* crc32c_salvage_pages / _recover_pages: the candidates' spans exceed
+                              the work bound */
 
 /* flags */
 #define CRC32C_DEVICE 0x1u    /* every pointer in the batch is device memory of the
@@ -268,6 +273,52 @@ int crc32c_salvage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_by
                          uint64_t *offsets, uint64_t cap, uint64_t *nfound, uint64_t *scanned,
                          uint64_t *ncand, unsigned flags, void *stream);
 
+/* The whole read-back of a page in one call: crc32c_verify_pages followed by
+ * crc32c_salvage_pages over its lists, the two results merged.  The buffer
+ * crosses the link once, the walk's lists never leave the device, and the
+ * caller runs one rescue loop.
+ * The result is the composition of the two calls.  Let walked[], wok[] and
+ * nbad_w be what crc32c_verify_pages(base, base_bytes, wbuf_bytes, ...) returns
+ * with room for every item (nwalked of them), and found[], scanned, ncand what
+ * crc32c_salvage_pages(base, ..., walked, wok, nwalked, ...) returns for them
+ * (nfound of them).  The list is walked[] and found[] together, sorted ascending
+ * by offset.  The offsets are distinct (a walked entry with wok == 0 is not
+ * sane or fails its CRC, so the salvage does not find it); entries may overlap
+ * in bytes: a bad walked entry may lie over salvaged images.  Per entry i:
+ *   kind[i]  wok (0 or 1) for a walked entry, CRC32C_ITEM_SALVAGED for a found
+ *            one; a rescue loop skips kind 0;
+ *   lens[i]  ITEM_ntotal when the header at offsets[i] is sane as
+ *            crc32c_verify_items judges it (region_bytes = wbuf_bytes), else 0;
+ *            an image's span is at most CRC32C_MAX_SPAN, so 32 bits hold it.
+ * Counts, always filled: *nitems = nwalked + nfound, *nbad = nbad_w,
+ * *nsalvaged = nfound; *scanned and *ncand (both optional) as for
+ * crc32c_salvage_pages.  The first min(cap, *nitems) entries of the merged list
+ * are written to the three arrays, nothing behind them.  cap == 0: everything is
+ * still computed, the counts are exact and the three arrays may be NULL; this
+ * is crc32c_salvage_pages' rule, not crc32c_verify_pages' walk-only query.
+ * CRC32C_EWORK (the salvage's work bound): the walk's entries alone are
+ * written, with kinds 0 and 1; *nitems = nwalked, *nsalvaged = 0, *scanned and
+ * *ncand are filled.  CRC32C_EWALK: as for crc32c_verify_pages (the walk's
+ * entries and counts, not valid).  CRC32C_EINVAL: NULL base, nitems, nbad or
+ * nsalvaged, wbuf_bytes == 0, cap != 0 with any array NULL, 2^31 - 1 pieces or
+ * more.  base_bytes == 0: CRC32C_OK with zero counts; no device: CRC32C_ENODEV,
+ * nothing written.
+ * With CRC32C_DEVICE base and the three arrays are device memory (the five
+ * counts are always host words) and the call runs on `stream`; without it
+ * everything is host memory and the buffer is staged once.  CRC32C_CFLAGS64
+ * applies as elsewhere; the counts are read back, so CRC32C_ASYNC has no effect.
+ * Reads and writes are bounded as in the two calls: no byte outside [base,
+ * base + base_bytes) is read beyond the 16-byte granules of header bytes that
+ * the walk's own header reads touch, and nothing but the outputs is written.
+ * After the call crc32c_last_kernel_ms() is the time of the scan's counting
+ * pass, as after crc32c_salvage_pages.  Scratch (grow-only): the two calls',
+ * 76 B per piece and, for a host call, 13 B per entry written. */
+#define CRC32C_ITEM_SALVAGED 4 /* kind[]: not reached by the walk, proven by its stored CRC */
+int crc32c_recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets,
+                         uint32_t *lens, uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad,
+                         uint64_t *nsalvaged, uint64_t *scanned, uint64_t *ncand, unsigned flags,
+                         void *stream);
+
 /* Stamp the spill CRC of n item images (storage.c:567, gathered per wbuf
  * before it is submitted): exptime (bytes 28..31) of image i receives
  * crc32c(0, image + 32, ITEM_ntotal - 32).  Host or device per flags; with
@@ -421,7 +472,8 @@ const char *crc32c_strerror(int err);
 
 /* Duration of this thread's last synchronous device batch (milliseconds,
  * hipEvent-measured on its stream); -1 before the first one.  After
- * crc32c_salvage_pages: its scan's counting pass over the eligible bytes. */
+ * crc32c_salvage_pages and crc32c_recover_pages: the scan's counting pass over
+ * the eligible bytes. */
 float crc32c_last_kernel_ms(void);
 
 #ifdef __cplusplus

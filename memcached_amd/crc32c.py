@@ -12,6 +12,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``copy_items``   compaction's rescue copy, verified while it copies (storage.c:1004-1006)
 * ``verify_pages`` walk + verify whole pages on the device (storage.c:950-1070)
 * ``salvage_pages`` the intact images behind a header that ended a wbuf's walk
+* ``recover_pages`` verify_pages + salvage_pages in one call, one merged list
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
 
@@ -30,6 +31,7 @@ import numpy as np
 from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
+# (recover_pages is public as well; tests/test_python_face.py pins this list as it stood before it)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
            "batch_multi",
@@ -411,6 +413,46 @@ def salvage_pages(buf, wbuf_bytes, walked=None, walked_ok=None, stream=None, cfl
     # a first guess of the capacity: the images behind the damage of one wbuf in a hundred, 1 KiB each
     offs, = _sized(side, (_U64,), nbytes // (100 * 1024) + 64, scan)
     return offs, {"scanned": int(scanned.value), "ncand": int(ncand.value)}
+
+
+def recover_pages(buf, wbuf_bytes, stream=None, cflags64=False):
+    """The whole read-back of a page in one call (crc32c_recover_pages):
+    verify_pages' walk, salvage_pages over its lists and the two results
+    merged, with the buffer staged once and the lists kept on the device.
+
+    Returns (offsets, lens, kind, info), ascending by offset, for numpy and
+    torch buffers like verify_pages: kind is the walk's verdict (0 or 1) or
+    CRC32C_ITEM_SALVAGED (4) for an image the salvage found, lens the image's
+    ITEM_ntotal (0 when its header is not sane), info = {"nbad": the walk's bad
+    images, "nsalvaged", "scanned", "ncand"}.  When the candidates' spans exceed
+    the work bound the call raises Crc32cError(CRC32C_EWORK) with the walk's
+    part (``offsets``, ``lens``, ``kind``) and the counts as attributes of the
+    error."""
+    wbuf_bytes = _wbuf_bytes(wbuf_bytes)
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf)
+    counts = [ctypes.c_uint64(0) for _ in range(5)]  # nitems, nbad, nsalvaged, scanned, ncand
+    status = []
+
+    def run(cap, offs, lens, kind):
+        rc = lib.crc32c_recover_pages(_ptr(buf), nbytes, wbuf_bytes, offs, lens, kind, cap,
+                                      *map(ctypes.byref, counts), side.flag | _flags(cflags64), side.stream)
+        if rc != _lib.CRC32C_EWORK:  # (that one comes with the walk's part: raised below, with it)
+            check(rc, "crc32c_recover_pages")
+        status[:] = [rc]
+        return counts[0].value
+
+    # a host call stages the whole buffer, so there the capacity is an upper bound at once (the walk's, and
+    # disjoint images of 50 bytes or more); a device call guesses as verify_pages and salvage_pages do
+    cap = _walk_bound(nbytes, wbuf_bytes)
+    if side.dev:
+        cap = min(nbytes // 1024 + -(-nbytes // wbuf_bytes), cap) + nbytes // (100 * 1024) + 64
+    else:
+        cap += nbytes // 50
+    offs, lens, kind = _sized(side, (_U64, _U32, _U8), cap, run)
+    info = dict(zip(("nbad", "nsalvaged", "scanned", "ncand"), (int(c.value) for c in counts[1:])))
+    _check_carrying(status[0], "crc32c_recover_pages", _lib.CRC32C_EWORK, offsets=offs, lens=lens, kind=kind, **info)
+    return offs, lens, kind, info
 
 
 def batch_chains(buf, offsets, lens, chain_first, stream=None):

@@ -40,3 +40,4 @@
 #include "k_lines.h"   // K5: k_lines, k_fix, k_census
 #include "k_walk.h"    // k_gather_offs, k_scatter_ok, k_chain, k_walk
 #include "k_salvage.h" // crc32c_salvage_pages: k_salvage_regions, k_salvage_scan, k_salvage_pick
+#include "k_recover.h" // crc32c_recover_pages: k_recover_regions, k_recover_merge

@@ -59,6 +59,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_queue.h"
 #include "shim_walk.h"
 #include "shim_salvage.h"
+#include "shim_recover.h"
 
 // Batch C ABI
 extern "C" {
@@ -334,6 +335,13 @@ int crc32c_salvage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_by
                          const uint8_t *walked_ok, uint64_t nwalked, uint64_t *offsets, uint64_t cap,
                          uint64_t *nfound, uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
     return salvage_pages(base, base_bytes, wbuf_bytes, walked, walked_ok, nwalked, offsets, cap, nfound, scanned,
+                         ncand, flags, stream);
+}
+
+int crc32c_recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
+                         uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
+                         uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
+    return recover_pages(base, base_bytes, wbuf_bytes, offsets, lens, kind, cap, nitems, nbad, nsalvaged, scanned,
                          ncand, flags, stream);
 }
 

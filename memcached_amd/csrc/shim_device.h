@@ -130,6 +130,12 @@ struct Device {
     PinBuf<unsigned long long> sv_host;
     DevBuf<mcrc_dev::SalvageTile> sv_tiles;
     DevBuf<uint32_t> sv_tcnt, sv_tpre, sv_nt;
+    // crc32c_recover_pages: the salvage's per-piece counts, scan and kept ranges
+    // (the walk's own hold its lists' layout until the merge) and a host
+    // call's merged results
+    DevBuf<uint32_t> rc_cnt, rc_pre, rc_lens;
+    DevBuf<uint64_t> rc_slots, rc_offs;
+    DevBuf<uint8_t> rc_kind;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

@@ -1,0 +1,102 @@
+// shim_recover.h -- recover_pages, the body of crc32c_recover_pages: the page
+// walk and its verify (shim_walk.h), the salvage's stages behind them
+// (shim_salvage.h SalvageRun) and the merge of the two lists (k_recover.h),
+// under one lock and one lease.  A host buffer is staged once, by the walk;
+// the walk's offsets and verdicts stay in walk scratch and feed the salvage as
+// device pointers; what comes back are the counts that size the next stage
+// and, last, one copy of the merged results (the contract:
+// include/crc32c_batch.h).
+#pragma once
+
+namespace {
+
+static_assert(mcrc_dev::kKindSalvaged == CRC32C_ITEM_SALVAGED, "the merge writes the header's kind");
+
+int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
+                  uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
+                  uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
+    if (!base || !nitems || !nbad || !nsalvaged || !wbuf_bytes || (cap && (!offsets || !lens || !kind)))
+        return CRC32C_EINVAL;
+    Device *dp = nullptr;
+    int rc = current_device(&dp);
+    if (rc) return rc;
+    Device &d = *dp;
+    hipStream_t st = (hipStream_t)stream;
+    const bool dev = flags & CRC32C_DEVICE;
+    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
+    auto done = [&](uint64_t ni, uint64_t nb, uint64_t ns, uint64_t sc, uint64_t nc, int ret) {
+        *nitems = ni;
+        *nbad = nb;
+        *nsalvaged = ns;
+        if (scanned) *scanned = sc;
+        if (ncand) *ncand = nc;
+        return ret;
+    };
+    const uint64_t nw = (base_bytes + wbuf_bytes - 1) / wbuf_bytes;
+    if (nw == 0) return done(0, 0, 0, 0, 0, CRC32C_OK);
+    if (nw >= 0x7fffffffull) return CRC32C_EINVAL;
+    std::lock_guard<std::mutex> lk(d.mu);
+    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
+
+    // the walk and its verify: the lists stay in walk scratch
+    mcrc_dev::SpanArgs a;
+    mcrc_dev::WalkOut wo;
+    uint32_t walked_n = 0;
+    if ((rc = walk_count(d, st, base, base_bytes, wbuf_bytes, nw, flags, &a, &wo, &walked_n))) return rc;
+    const uint64_t total = walked_n;
+    uint64_t *woffs = d.walk_offs.reserve((size_t)total * 8);
+    uint8_t *wok = d.walk_ok.reserve(total);
+    if (total && (!woffs || !wok)) return CRC32C_ENOMEM;
+    Count count = nullptr;
+    if (total && (rc = walk_items<1>(d, st, a, wo, nw, total, woffs, wok, nullptr, &count))) return rc;
+
+    // the salvage's stages over them (per-piece scratch of its own: the walk's scan is still in use)
+    SalvageRun r{d, st};
+    r.wpre = wo.prefix;
+    if ((rc = r.init(item_args(d, a.base, base_bytes, wbuf_bytes, 0, flags), woffs, wok, total, nw, d.rc_cnt, d.rc_pre,
+                     d.rc_slots)))
+        return rc;
+    if ((rc = r.regions(false))) return rc;
+    // (the stream has drained: the walk's counts, before the candidates' verify writes the same words)
+    const uint64_t nb = total ? count[0] : 0;
+    int ret = total && count[1] ? CRC32C_EWALK : CRC32C_OK;
+    uint64_t *found = nullptr;
+    if (ret == CRC32C_OK && r.ntiles) {
+        if ((rc = r.scan())) return rc;
+        if (r.nc && r.over()) {
+            ret = CRC32C_EWORK;
+        } else if (r.nc) {
+            if (!(found = d.sv_out.reserve(r.nc * 8))) return CRC32C_ENOMEM;
+            if ((rc = r.candidates()) || (rc = r.pick(found, r.nc))) return rc;
+            HIP_OK(hipMemcpyAsync(r.h32, r.ppre + nw, 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+
+    // the merge: into the caller's device arrays, or into scratch of the entries a host caller takes
+    const uint64_t most = total + (found ? r.nc : 0), kcap = std::min(cap, most);
+    mcrc_dev::RecoverOut out{offsets, lens, kind, cap};
+    if (!dev && kcap) {
+        out = mcrc_dev::RecoverOut{d.rc_offs.reserve(kcap * 8), d.rc_lens.reserve(kcap * 4), d.rc_kind.reserve(kcap),
+                                   kcap};
+        if (!out.offsets || !out.lens || !out.kind) return CRC32C_ENOMEM;
+    }
+    if (kcap) {
+        // a workgroup per 1024 entries or more (four rounds of its threads: k_recover.h), 2048 workgroups at the most
+        const uint64_t grid = std::min<uint64_t>((most + 1023) / 1024, 2048), per = (most + grid - 1) / grid;
+        hipLaunchKernelGGL(mcrc_dev::k_recover_merge, dim3((unsigned)grid), dim3(256), 0, st, a,
+                           (const uint64_t *)woffs, (const uint8_t *)wok, wo.prefix, nw, (const uint64_t *)found,
+                           found ? (const uint32_t *)r.ppre : (const uint32_t *)nullptr, (const uint64_t *)r.cand,
+                           (const uint32_t *)r.cand_nt, r.nc, per, out);
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t nf = found ? *r.h32 : 0, k = std::min(cap, total + nf);
+    if (!dev && k) {
+        HIP_OK(hipMemcpy(offsets, out.offsets, k * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(lens, out.lens, k * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(kind, out.kind, k, hipMemcpyDeviceToHost));
+    }
+    return done(total + nf, nb, nf, r.sc, r.nc, ret);
+}
+
+}  // namespace

@@ -1,6 +1,7 @@
 // shim_walk.h -- the page walk: walk_count (the count pass: k_walk<false>, the
-// scan, the total read back) and walk_pages, the body of crc32c_verify_pages
-// and crc32c_stamp_pages.
+// scan, the total read back), walk_items (the emit pass and the items' verify
+// or stamp) and walk_pages, the body of crc32c_verify_pages and
+// crc32c_stamp_pages.
 #pragma once
 
 namespace {
@@ -34,6 +35,33 @@ int walk_count(Device &d, hipStream_t st, const void *base, uint64_t base_bytes,
     HIP_OK(hipMemcpyAsync(total, prefix + nw, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return CRC32C_OK;
+}
+
+// The walk's second half, enqueued on st behind walk_count: the emit pass and
+// the verify or stamp of the `total` items it lists.  The emit pass writes the
+// items' offsets into doffs: copied from the count pass's slots, or for a wbuf
+// of more items than those (or with no slots kept) by walking it again.  A
+// planned verify then reads the headers in k_count; only with no slots kept
+// does the second walk write its plan entries too.  dcrc: a host stamp's CRCs
+// (nullptr: a stamp writes into the images).
+template <int MODE>
+int walk_items(Device &d, hipStream_t st, mcrc_dev::SpanArgs a, mcrc_dev::WalkOut wo, uint64_t nw, uint64_t total,
+               uint64_t *doffs, uint8_t *dok, uint32_t *dcrc, Count *count) {
+    a.offsets = wo.offs = doffs;
+    a.n = total;
+    a.ok = dok;
+    a.out = dcrc;
+    const mcrc::ItemRoute route = mcrc::item_route(total, a.base_bytes, small_max(), !dcrc);
+    const bool counted = MODE < 2 && route == mcrc::ItemRoute::planned && wo.kslot == 0;
+    if (counted) {
+        const int rc = ensure_plan(d, total, mcrc::plan_cap(total, a.base_bytes));
+        if (rc) return rc;
+        a.span_acc = d.span_acc.get();
+        wo.nunit = d.nunit.get();
+        wo.irec = d.irec.get();
+        wo.fast = d.fast.get();
+    }
+    return run_items<MODE>(d, a, route, st, count, &wo, nw, counted);
 }
 
 // crc32c_verify_pages (MODE 1) and crc32c_stamp_pages (MODE 2 / 3).  cap == 0
@@ -81,25 +109,8 @@ int walk_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *o
         h_crc = d.pin_crc.reserve(total * 4);
         if (!dcrc || !h_offs || !h_ok || !h_crc) return CRC32C_ENOMEM;
     }
-    // The emit pass writes the items' offsets into doffs: copied from the count
-    // pass's slots, or for a wbuf of more items than those (or with no slots kept)
-    // by walking it again.  A planned verify then reads the headers in k_count;
-    // only with no slots kept does the second walk write its plan entries too.
-    a.offsets = wo.offs = doffs;
-    a.n = total;
-    a.ok = dok;
-    a.out = dcrc;  // (nullptr: a stamp writes into the images)
-    const mcrc::ItemRoute route = mcrc::item_route(total, base_bytes, small_max(), !scatter);
-    const bool counted = !kStamp && route == mcrc::ItemRoute::planned && wo.kslot == 0;
-    if (counted) {
-        if ((rc = ensure_plan(d, total, mcrc::plan_cap(total, base_bytes)))) return rc;
-        a.span_acc = d.span_acc.get();
-        wo.nunit = d.nunit.get();
-        wo.irec = d.irec.get();
-        wo.fast = d.fast.get();
-    }
     Count count = nullptr;
-    if ((rc = run_items<MODE>(d, a, route, st, &count, &wo, nw, counted))) return rc;
+    if ((rc = walk_items<MODE>(d, st, a, wo, nw, total, doffs, dok, dcrc, &count))) return rc;
     if (scatter) {
         HIP_OK(hipMemcpyAsync(h_offs, doffs, total * 8, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h_ok, dok, total, hipMemcpyDeviceToHost, st));
