@@ -35,6 +35,78 @@ constexpr uint32_t kK1RoundsMinSteps = 32;
 // long as it owes an arrival (floor(nsteps / S) <= floor(cg / S) times), and
 // makes up the rest after its last store (k_fixed.h).
 MCRC_HD uint64_t k1_rounds(uint64_t cg, uint32_t S) { return cg >= kK1RoundsMinSteps ? cg / S : 0; }
+// K1's order: which group (pair of items) a wave reads at which step of the
+// static part.  W = nwg wv waves (nwg workgroups of wv waves), every wave cg
+// steps: cg / 4 passes of K1's 4-step loop and a remainder of cg % 4 steps.
+//   ranges (O0)       wave w = wv b + t streams the contiguous range r of cg
+//                     groups, r = (w 65521) mod W: a bijection unless the prime
+//                     divides W, and then the deal is left unscrambled
+//   window by pass    workgroup b owns the wv cg contiguous groups of window rb
+//   (O2)              (b dealt through the same scramble over nwg, or b itself);
+//                     in pass q wave t reads the four groups
+//                     base + 4 wv q + 4 t + j: 32 KiB contiguous per wave and
+//                     pass, 32 wv KiB per workgroup and round.  The remainder:
+//                     base + 4 wv (cg / 4) + (cg % 4) t + j
+//   window by step    wave t reads base + wv s + t at step s: 8 wv KiB
+//   (O1)              contiguous per workgroup and step
+// The window orders run only in launches with lockstep rounds (cg >=
+// kK1RoundsMinSteps): a window is read together only by waves that are paced
+// together.  Shorter launches keep the ranges.
+enum K1Order : uint32_t { kK1OrderRanges = 0, kK1OrderWindowStep = 1, kK1OrderWindowPass = 2 };
+MCRC_HD uint64_t k1_scramble(uint64_t i, uint64_t n) { return n % 65521u ? (i * 65521u) % n : i; }
+MCRC_HD K1Order k1_order_for(K1Order o, uint64_t cg) { return cg >= kK1RoundsMinSteps ? o : kK1OrderRanges; }
+// One wave's walk: step j of pass q reads group first + q pstep + j sstep, step
+// j of the remainder rfirst + j sstep; a group at or past end (or past the
+// batch) is not the wave's and is not read.
+struct K1Walk {
+    uint64_t first, sstep, pstep, rfirst, end;
+};
+// (o: the order that runs, k1_order_for's; scramble: deal the windows through
+// k1_scramble -- the ranges always are)
+MCRC_HD K1Walk k1_walk(K1Order o, bool scramble, uint32_t b, uint32_t t, uint32_t nwg, uint32_t wv, uint64_t cg) {
+    const uint64_t whole = cg & ~3ull, rem = cg & 3u;
+    K1Walk k;
+    if (o == kK1OrderRanges) {
+        k.first = k1_scramble(b * wv + t, (uint64_t)nwg * wv) * cg;
+        k.sstep = 1, k.pstep = 4;
+        k.rfirst = k.first + whole;
+        k.end = k.first + cg;
+        return k;
+    }
+    const uint64_t base = (scramble ? k1_scramble(b, nwg) : b) * wv * cg;
+    k.pstep = 4ull * wv;
+    if (o == kK1OrderWindowPass) {
+        k.first = base + 4ull * t;
+        k.sstep = 1;
+        k.rfirst = base + wv * whole + rem * t;
+        k.end = k.rfirst + rem;  // (no remainder: the window's end)
+    } else {
+        k.first = base + t;
+        k.sstep = wv;
+        k.rfirst = base + wv * whole + t;
+        k.end = base + wv * cg;
+    }
+    return k;
+}
+// The group that wave slot t of workgroup b reads at step j (0-3) of pass q
+// (q = cg / 4: the remainder, j < cg % 4).
+MCRC_HD uint64_t k1_group(K1Order o, bool scramble, uint32_t b, uint32_t t, uint64_t q, uint32_t j, uint32_t nwg,
+                          uint32_t wv, uint64_t cg) {
+    const K1Walk k = k1_walk(o, scramble, b, t, nwg, wv, cg);
+    return (q < cg / 4 ? k.first + q * k.pstep : k.rfirst) + j * k.sstep;
+}
+// The order the product runs, and whether its windows are dealt scrambled.
+// Libraries alternated with the parent's (the ranges) under bench.py on one
+// box, ms per launch, medians (profiles/k1_order_ab.jsonl, four sessions; K1
+// in every order in one process: profiles/k1_order_waves.txt):
+//   items    ranges   window by pass     the same, scrambled   window by step (one process)
+//   1 Mi     0.6267   0.6103 (-2.6 %)    level (0.6121 beside 0.6119)   -2.0 % (pass beside it -3.2 %)
+//   4 Mi     2.5225   2.4402 (-3.3 %)    2.4417                -1.4 % (-2.2 %)
+//   320 Ki   0.2045   0.2030 (-0.7 %)    0.2027                -1.3 % (-1.7 %)
+// faster than the ranges in every round of every session (28 at 1 Mi items).
+// The scramble buys nothing for windows, so they are dealt in launch order.
+constexpr K1Order kK1Order = kK1OrderWindowPass;
+constexpr bool kK1WindowScramble = false;
 // K1's claimed tail: the XCDs do not run at one rate, so equal static shares
 // leave the faster ones idle at the end of a launch.  The last 1 / 2^kK1TailShift
 // of every range goes into a pool instead, cut into chunks of kK1TailSteps

@@ -59,7 +59,10 @@ struct K1NoProbe {
 // ctl: null, or the launch's counters (K1Ctl, k_consts.h): the launch then
 // runs k1_tail_split's static part in the loop below and claims the pool's
 // chunks behind it ("The claimed tail").
-template <bool CRCIN, bool NT, class Probe>
+// ORD, SCR: the order of the static part (K1Order, k_consts.h) in a launch with
+// lockstep rounds, and whether its windows are dealt scrambled; the product's
+// are kK1Order and kK1WindowScramble, the tools instantiate the others.
+template <bool CRCIN, bool NT, class Probe, K1Order ORD = kK1Order, bool SCR = kK1WindowScramble>
 __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, uint64_t stride, uint64_t nitems,
                                              const uint4 *__restrict__ img, const uint32_t *__restrict__ crc_in,
                                              uint32_t *__restrict__ out, uint32_t nthreads, K1Ctl *__restrict__ ctl,
@@ -72,28 +75,33 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     const uint64_t waves = nthreads >> 6;
     const uint64_t gstep = gridDim.x * waves;
     const uint64_t ngroups = (nitems + IPW - 1) / IPW;
-    // wave-uniform (SGPR) group index: the loop exits are then scalar
-    // branches, and the waitcnt pass sees one path into the loop header (a
-    // divergent exit merged an un-waited path there and forced vmcnt(0),
-    // which drained the prefetched step).
-    uint64_t grp = __builtin_amdgcn_readfirstlane(blockIdx.x * (uint32_t)waves + (threadIdx.x >> 6));
-    // the ranges dealt to the waves in a scrambled order: wave w takes range
-    // (w * 65521) mod W (65521 is prime: a bijection unless it divides W), so
-    // a CU's 16 waves stream ranges far apart rather than 16 neighbouring
-    // MiB: -0.6 % at 1 and 4 Mi items in every round
-    // (profiles/r04_ablations/k1_range_order_ab.txt)
-    if (gstep % 65521u) grp = (grp * 65521u) % gstep;
-    // wave w takes the contiguous groups [w cg, (w + 1) cg): 1.0-1.4 % faster
-    // than the grid-stride order at 1 Mi items, 0.6-3.7 % at 4 Mi, on two
-    // boxes (profiles/r04_ablations/k1_chunk_and_census_ab.txt,
-    // k1_item_order_ab.txt); a range per workgroup with its waves interleaved
-    // was 4.5 % slower
     // (with a claimed tail: the static part's full ranges of cg_s steps)
     const bool tail = ctl != nullptr;  // (a kernel argument: wave-uniform)
     const K1Tail tl = tail ? k1_tail_split(ngroups, gstep) : K1Tail{0, 0, 0};
     const uint64_t cg = tail ? tl.cg_s : (ngroups + gstep - 1) / gstep;
-    uint64_t gend = min((grp + 1) * cg, ngroups);
-    grp *= cg;
+    // The order (k1_walk, k_consts.h).  A launch with
+    // lockstep rounds runs ORD, the product a window per workgroup read pass by
+    // pass: its waves stay within a pass of each other, so the workgroup reads
+    // 512 KiB of neighbouring addresses together, 32 KiB per wave: 2.6 % faster
+    // than the ranges at 1 Mi items, 3.3 % at 4 Mi, in every round
+    // (profiles/k1_order_ab.jsonl; the bulk rate 7.30 against 6.99 TB/s,
+    // profiles/k1_order_timeline.txt).  A launch too short for rounds streams a
+    // contiguous range per wave, the ranges dealt scrambled so that a CU's 16
+    // waves read far apart: its waves drift, and what they would share is then
+    // read microseconds apart.
+    // wave-uniform (SGPR) group index: the loop exits are then scalar
+    // branches, and the waitcnt pass sees one path into the loop header (a
+    // divergent exit merged an un-waited path there and forced vmcnt(0),
+    // which drained the prefetched step).
+    const uint32_t wslot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const K1Order ord = k1_order_for(ORD, cg);
+    const K1Walk wk = k1_walk(ord, SCR, blockIdx.x, wslot, gridDim.x, (uint32_t)waves, cg);
+    uint64_t grp = wk.first;
+    // (the strides between a pass's steps and between passes: constants where
+    // the build's orders leave no choice)
+    const uint64_t ss = ORD == kK1OrderWindowStep ? wk.sstep : 1;
+    const uint64_t ps = ORD == kK1OrderRanges ? 4 : wk.pstep;
+    uint64_t gend = min(wk.end, ngroups);
     // Lockstep rounds: the barriers this wave still owes its workgroup, from
     // cg alone (k1_rounds, k_consts.h), so every wave of the grid starts with
     // the same count -- also a wave whose range is empty or cut short at the
@@ -116,7 +124,10 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     // not used): re-reading the wave's last group fetched it from HBM again
     // (non-temporal loads), 0.7 % of the launch's bytes, and clamping every
     // wave to the batch's last group made 4096 waves read the same 8 KiB at
-    // the end of the launch.  The sched_barrier keeps the loads where they
+    // the end of the launch.  So does a group of a window that lies past the
+    // batch (a launch without the claimed tail): its pass runs on the image,
+    // the stores' guard drops its items, and the wave arrives at its round's
+    // barrier like the others.  The sched_barrier keeps the loads where they
     // are issued: left alone, the scheduler sinks them into the chains and
     // the next half waits on loads issued moments before.
     auto ldh = [&](K1Half &r, uint64_t gi, int q) {
@@ -150,8 +161,8 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     // Step k's halves live in h0/h1 (k even) or h2/h3 (k odd).  Before step k
     // is checksummed, its two halves and step k + 1's first are issued; each
     // half's checksum is preceded by the issue of the half three later.
-    // (even step k at grp: h0/h1 -> issue h3 (k+1, B), h0 (k+2, A)); a and b
-    // are the groups of steps k + 1 and k + 2: s + 1 and s + 2 inside a range
+    // (even step k: h0/h1 -> issue h3 (k+1, B), h0 (k+2, A)); a and b are the
+    // groups of steps k + 1 and k + 2: s + ss and s + 2 ss inside a pass
     auto step_even2 = [&](uint64_t a, uint64_t b) {
         ldh(h3, a, 1);
         const uint32_t u0 = half0(h0);
@@ -164,34 +175,38 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
         ldh(h2, b, 0);
         return part0(u0, h3);
     };
-    auto step_even = [&](uint64_t s) { return step_even2(s + 1, s + 2); };
-    auto step_odd = [&](uint64_t s) { return step_odd2(s + 1, s + 2); };
-    // the stores of a 4-step pass over the groups first .. first + 3
-    auto store4 = [&](uint32_t vab, uint32_t vc, uint32_t vd, uint64_t first) {
+    // the stores of a 4-step pass over the groups first + j sp
+    auto store4 = [&](uint32_t vab, uint32_t vc, uint32_t vd, uint64_t first, uint64_t sp) {
         const uint32_t raw = group_reduce32_quad_span(vab, group_pair_level1(vc, vd, lane), lane);
-        const uint64_t item = item_of(first + (li & 3u));
+        const uint64_t item = item_of(first + (li & 3u) * (uint32_t)sp);
         if (li < 4 && item < nitems) out[item] = ~raw;
     };
     uint64_t ran = 0;  // steps run (for the probe)
     if (busy) {
         // (<= cg; with a claimed tail the range's last pass is left to the
-        // tail loop, whose first chunk it is)
-        const uint64_t nsteps = gend - grp - (tail ? 4u : 0u);
+        // tail loop, whose first chunk it is.  A window's wave runs all its cg
+        // steps, those past the batch on the table image.)
+        const uint64_t nsteps = (ord != kK1OrderRanges ? cg : gend - grp) - (tail ? 4u : 0u);
+        // (the steps in whole passes, the tail loop's one included)
+        const uint64_t nwhole = (nsteps + (tail ? 4u : 0u)) & ~3ull;
         ldh(h0, grp, 0);
         ldh(h1, grp, 1);
-        ldh(h2, grp + 1, 0);
+        ldh(h2, grp + ss, 0);
         // One exit, at the bottom of each loop: a break between the halves would
         // give the loop header a second (un-waited) predecessor, and the waitcnt
         // pass would then drain every prefetched load there.
         uint64_t k = 0;
         for (; k + 4 <= nsteps; k += 4) {
-            const uint32_t va = step_even(grp);
-            const uint32_t vb = step_odd(grp + 1);
+            // the next pass: ps on, or behind the last whole pass the remainder
+            // (both grp + 4 in a range)
+            const uint64_t nxt = ord == kK1OrderRanges || k + 8 <= nwhole ? grp + ps : wk.rfirst;
+            const uint32_t va = step_even2(grp + ss, grp + 2 * ss);
+            const uint32_t vb = step_odd2(grp + 2 * ss, grp + 3 * ss);
             const uint32_t vab = group_pair_level1(va, vb, lane);
-            const uint32_t vc = step_even(grp + 2);
-            const uint32_t vd = step_odd(grp + 3);
-            store4(vab, vc, vd, grp);
-            grp += 4;
+            const uint32_t vc = step_even2(grp + 3 * ss, nxt);
+            const uint32_t vd = step_odd2(nxt, nxt + ss);
+            store4(vab, vc, vd, grp, ss);
+            grp = nxt;
             // (the three half-steps in flight stay in flight across it)
             if ((k + 4) % kK1RoundSteps == 0 && owed) {
                 k1_round_barrier();
@@ -201,15 +216,15 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
         }
         ran = k;
         for (; k + 2 <= nsteps; k += 2) {
-            const uint32_t va = step_even(grp);
-            const uint32_t vb = step_odd(grp + 1);
+            const uint32_t va = step_even2(grp + ss, grp + 2 * ss);
+            const uint32_t vb = step_odd2(grp + 2 * ss, grp + 3 * ss);
             const uint32_t raw = group_reduce32_pair_span(va, vb, lane);
-            const uint64_t item = item_of(li == 0 ? grp : grp + 1);
+            const uint64_t item = item_of(li == 0 ? grp : grp + ss);
             if (li < 2 && item < nitems) out[item] = ~raw;
-            grp += 2;
+            grp += 2 * ss;
         }
         if (nsteps & 1) {
-            const uint32_t raw = group_reduce32_single_span(step_even(grp), lane);
+            const uint32_t raw = group_reduce32_single_span(step_even2(grp + ss, grp + 2 * ss), lane);
             const uint64_t item = item_of(grp);
             if (li == 0 && item < nitems) out[item] = ~raw;
         }
@@ -231,7 +246,7 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
     // chunk may be cut: its missing groups load the table image and their
     // items lie past nitems, so the stores' guard drops them.
     if (tail) {
-        const uint32_t t = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const uint32_t t = wslot;
         const uint64_t mine = k1_tail_pool_chunks(tl.nchunks, t);
         gend = ngroups;
         glast = ngroups - 1;
@@ -242,20 +257,23 @@ __device__ __forceinline__ void k_fixed_body(const uint8_t *__restrict__ base, u
         typedef __attribute__((address_space(1))) uint32_t gu32;
         gu32 *head = (gu32 *)&ctl->head[t].v;
         asm volatile("" : "+v"(head));
-        uint64_t cur = grp, nxt;
+        // (sp: the stride of the chunk's steps; the static part's last pass has
+        // its order's, a claimed chunk is four neighbouring groups)
+        uint64_t cur = grp, nxt, sp = ss;
         do {
             uint32_t i = 0;
             if (lane == 0) i = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t va = step_even(cur);
-            const uint32_t vb = step_odd(cur + 1);
+            const uint32_t va = step_even2(cur + sp, cur + 2 * sp);
+            const uint32_t vb = step_odd2(cur + 2 * sp, cur + 3 * sp);
             const uint32_t vab = group_pair_level1(va, vb, lane);
             i = __builtin_amdgcn_readfirstlane(i);
             // (ngroups: no chunk; it and ngroups + 1 load the table image)
             nxt = i < mine ? tl.pool0 + ((uint64_t)i * kK1TailPools + t) * kK1TailSteps : ngroups;
-            const uint32_t vc = step_even2(cur + 3, nxt);
+            const uint32_t vc = step_even2(cur + 3 * sp, nxt);
             const uint32_t vd = step_odd2(nxt, nxt + 1);
-            store4(vab, vc, vd, cur);
+            store4(vab, vc, vd, cur, sp);
             cur = nxt;
+            if constexpr (ORD == kK1OrderWindowStep) sp = 1;
             ran += 4;
             probe.steps(ran);
         } while (nxt < ngroups);

@@ -6,6 +6,10 @@
 // wave's XCC id and hardware id and the steps it ran (its claimed chunks
 // included).  Both kernels get a counter block (K1Ctl) when the launch is long
 // enough for the claimed tail; K1_TAIL=0 in the environment runs them without.
+// Both run the product's order (kK1Order, kK1WindowScramble; k_consts.h) unless
+// K1_ORDER (0 ranges, 1 window by step, 2 window by pass) and K1_SCRAMBLE (0 / 1:
+// the windows dealt in launch order / scrambled) name another; the order that ran
+// is printed.
 // Lane 0 writes the stamps with plain vector stores.  The stamped launch's CRCs are checked equal to the product
 // kernel's on the same batch.  Printed per item count:
 //   - the product's and the stamped kernel's event times (what the stamps cost)
@@ -75,6 +79,7 @@ struct StampProbe {
     }
 };
 
+template <int ORD, bool SCR>
 __global__ __launch_bounds__(1024) void k_fixed_stamped(const uint8_t *__restrict__ base, uint64_t stride,
                                                         uint64_t nitems, const uint4 *__restrict__ img,
                                                         uint32_t *__restrict__ out, K1Ctl *__restrict__ ctl, Stamp *st,
@@ -85,8 +90,33 @@ __global__ __launch_bounds__(1024) void k_fixed_stamped(const uint8_t *__restric
     extern __shared__ __attribute__((aligned(16))) char smem[];
     load_tables(smem, img, kLdsImageK1Bytes);
     probe.mark(1);
-    k_fixed_body<false, true>(base, stride, nitems, img, nullptr, out, blockDim.x, ctl, probe);
+    k_fixed_body<false, true, StampProbe, (K1Order)ORD, SCR>(base, stride, nitems, img, nullptr, out, blockDim.x, ctl, probe);
 }
+// (the product's kernel, k_fixed, in the same order)
+template <int ORD, bool SCR>
+__global__ __launch_bounds__(1024) void k_fixed_plain(const uint8_t *__restrict__ base, uint64_t stride, uint64_t nitems,
+                                                      const uint4 *__restrict__ img, uint32_t *__restrict__ out,
+                                                      K1Ctl *__restrict__ ctl) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    load_tables(smem, img, kLdsImageK1Bytes);
+    k_fixed_body<false, true, K1NoProbe, (K1Order)ORD, SCR>(base, stride, nitems, img, nullptr, out, blockDim.x, ctl,
+                                                            K1NoProbe{});
+}
+struct OrderKernels {
+    int order;
+    bool scramble;
+    const char *name;
+    const void *stamped, *plain;
+};
+#define ORDER_KERNELS(O, S, NAME) \
+    OrderKernels { O, S, NAME, (const void *)k_fixed_stamped<O, S>, (const void *)k_fixed_plain<O, S> }
+static const OrderKernels kOrders[] = {
+    ORDER_KERNELS(0, true, "ranges, dealt scrambled"),
+    ORDER_KERNELS(1, false, "window by step, windows in launch order"),
+    ORDER_KERNELS(1, true, "window by step, windows dealt scrambled"),
+    ORDER_KERNELS(2, false, "window by pass, windows in launch order"),
+    ORDER_KERNELS(2, true, "window by pass, windows dealt scrambled"),
+};
 
 __global__ void fill(uint32_t *p, uint64_t n) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -130,8 +160,9 @@ struct Wave {
     double t_entry, t_tables, t_end;  // us since the first entry
 };
 
-static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t slots, bool claimed) {
+static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t slots, bool claimed, const OrderKernels &ok) {
     const uint64_t nw = (uint64_t)grid * 16, ngroups = (n + 1) / 2, cg = (ngroups + nw - 1) / nw;
+    const K1Order run = k1_order_for((K1Order)ok.order, cg);
     uint64_t t0 = ~0ull;
     for (uint64_t w = 0; w < nw; ++w) t0 = std::min(t0, st[w * slots].rt);
     auto us = [&](uint64_t rt) { return (double)(rt - t0) / 100.0; };
@@ -142,8 +173,9 @@ static void analyse(uint64_t n, int grid, const std::vector<Stamp> &st, uint32_t
         Wave &x = wv[w];
         x.wg = (uint32_t)(w / 16);
         x.xcc = (uint32_t)r[3].sc & 15u;
-        uint64_t grp = nw % 65521u ? (w * 65521u) % nw : w;  // K1's range split (k_fixed.h)
-        const uint64_t g0 = grp * cg, g1 = std::min((grp + 1) * cg, ngroups);
+        // K1's walk (k1_walk, k_consts.h): a range is cut at the batch's end, a window's wave runs all its steps
+        const K1Walk wk = k1_walk(run, ok.scramble, (uint32_t)(w / 16), (uint32_t)(w % 16), (uint32_t)grid, 16, cg);
+        const uint64_t g0 = wk.first, g1 = run == kK1OrderRanges ? std::min(wk.end, ngroups) : g0 + cg;
         // (with the claimed tail: what the wave counted, whole passes)
         x.nsteps = claimed ? r[4].rt : g0 < ngroups ? g1 - g0 : 0;
         x.t_entry = us(r[0].rt), x.t_tables = us(r[1].rt), x.t_end = us(r[2].rt);
@@ -288,10 +320,22 @@ int main(int argc, char **argv) {
     CHECK(hipGetDeviceProperties(&p, 0));
     const int cus = p.multiProcessorCount;
     const bool want_tail = !(getenv("K1_TAIL") && atoi(getenv("K1_TAIL")) == 0);
+    const int want_order = getenv("K1_ORDER") ? atoi(getenv("K1_ORDER")) : (int)kK1Order;
+    const bool want_scr = want_order == 0 || (getenv("K1_SCRAMBLE") ? atoi(getenv("K1_SCRAMBLE")) != 0 : kK1WindowScramble);
+    const OrderKernels *ok = nullptr;
+    for (const OrderKernels &k : kOrders)
+        if (k.order == want_order && k.scramble == want_scr) ok = &k;
+    if (!ok) {
+        fprintf(stderr, "K1_ORDER must be 0, 1 or 2\n");
+        return 2;
+    }
     printf("device %s  CUs %d  K1 lockstep round: %u steps; claimed tail %s (from %u steps per wave, 1/%u of a range, chunks of "
            "%u steps)\n",
            p.gcnArchName, cus, (unsigned)kK1RoundSteps, want_tail ? "on" : "off", (unsigned)kK1TailMinSteps,
            1u << kK1TailShift, (unsigned)kK1TailSteps);
+    printf("K1 order: %s%s, in launches of at least %u steps per wave (shorter ones: ranges)\n", ok->name,
+           want_order == (int)kK1Order && (want_order == 0 || want_scr == kK1WindowScramble) ? " (the product's)" : "",
+           (unsigned)kK1RoundsMinSteps);
     K1Ctl *dctl;
     CHECK(hipMalloc(&dctl, sizeof(K1Ctl)));
     CHECK(hipMemset(dctl, 0, sizeof(K1Ctl)));
@@ -307,11 +351,10 @@ int main(int argc, char **argv) {
     uint4 *dimg;
     CHECK(hipMalloc(&dimg, img.size() * 4));
     CHECK(hipMemcpy(dimg, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-    CHECK(hipFuncSetAttribute((const void *)k_fixed<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsImageK1Bytes));
-    CHECK(hipFuncSetAttribute((const void *)k_fixed_stamped, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsImageK1Bytes));
-    for (uint64_t n : sizes) {
+    CHECK(hipFuncSetAttribute(ok->plain, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsImageK1Bytes));
+    CHECK(hipFuncSetAttribute(ok->stamped, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsImageK1Bytes));
+    const uint64_t stride = kItemBytes;
+    for (const uint64_t n : sizes) {
         const int grid = mcrc::grid_for(cus, n);
         const uint64_t nw = (uint64_t)grid * 16, cg = ((n + 1) / 2 + nw - 1) / nw;
         // (a wave that claims runs more steps than cg: rows of twice that, and
@@ -322,12 +365,13 @@ int main(int argc, char **argv) {
         CHECK(hipMalloc(&st, nw * slots * sizeof(Stamp)));
         CHECK(hipMemset(st, 0, nw * slots * sizeof(Stamp)));
         auto product = [&] {
-            hipLaunchKernelGGL((k_fixed<false, true>), dim3(grid), dim3(1024), kLdsImageK1Bytes, 0, d, kItemBytes, n, dimg,
-                               nullptr, out_ref, ctl);
+            void *args[] = {(void *)&d, (void *)&stride, (void *)&n, (void *)&dimg, (void *)&out_ref, (void *)&ctl};
+            CHECK(hipLaunchKernel(ok->plain, dim3(grid), dim3(1024), args, kLdsImageK1Bytes, 0));
         };
         auto stamped = [&] {
-            hipLaunchKernelGGL(k_fixed_stamped, dim3(grid), dim3(1024), kLdsImageK1Bytes, 0, d, kItemBytes, n, dimg, out, ctl,
-                               st, slots);
+            void *args[] = {(void *)&d,   (void *)&stride, (void *)&n,  (void *)&dimg,
+                            (void *)&out, (void *)&ctl,    (void *)&st, (void *)&slots};
+            CHECK(hipLaunchKernel(ok->stamped, dim3(grid), dim3(1024), args, kLdsImageK1Bytes, 0));
         };
         // clock settle: 300 ms of back-to-back product launches
         const auto c0 = std::chrono::steady_clock::now();
@@ -353,7 +397,7 @@ int main(int argc, char **argv) {
         printf("n %llu: stamped CRCs %s the product kernel's\n", (unsigned long long)n, same ? "equal" : "DIFFER FROM");
         std::vector<Stamp> hs(nw * slots);
         CHECK(hipMemcpy(hs.data(), st, hs.size() * sizeof(Stamp), hipMemcpyDeviceToHost));  // (the last stamped launch)
-        analyse(n, grid, hs, slots, ctl != nullptr);
+        analyse(n, grid, hs, slots, ctl != nullptr, *ok);
         fflush(stdout);
         CHECK(hipFree(st));
         if (!same) return 1;

@@ -11,8 +11,21 @@
 //   glds W8 S4096 B2   r05's best LDS-DMA stream (reference point)
 // Every load-only mode writes each item's XOR of its dwords (checked equal).
 //
+// MODE order (the default): which order of the batch the memory system
+// prefers (K1Order, k_consts.h), alternated in one process:
+//   ord ORDER [bar]    K1's load shape and ring (four half-steps of 4 KiB,
+//                      three in flight, nt), XOR instead of the chains, walked
+//                      in ORDER with a bare workgroup barrier every 4 steps
+//                      (bar) or none: ranges, pass (window by pass), step
+//                      (window by step); +s / +u: windows dealt scrambled / in
+//                      launch order
+//   K1 ORDER           k_fixed_body itself in ORDER, with the claimed tail
+//                      where the launch is long enough (CRCs checked equal to
+//                      the ranges')
+// MODE waves: the round-6 table above.
+//
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I memcached_amd/csrc tools/k1_waves.hip -o tools/k1_waves
-//   tools/k1_waves [REPS]
+//   tools/k1_waves [REPS] [order|waves] [ITEMS] [ROUNDS]
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -55,6 +68,85 @@ __device__ __forceinline__ uint32_t wave_xor32(uint32_t v) {
     v ^= __shfl_xor(v, 8);
     v ^= __shfl_xor(v, 16);
     return v;
+}
+
+// K1's walk without its chains: the ring of k_fixed_body (h0 .. h3, the half
+// three later issued before each half is folded), every group's two items
+// XORed.  n: items, a multiple of 8 x the grid's waves (whole passes, full
+// windows).
+struct HalfX {
+    uint4 v[4];
+};
+template <int ORD, bool SCR, bool BAR>
+__global__ __launch_bounds__(1024) void ord_ring(const uint8_t *__restrict__ base, uint64_t n,
+                                                 uint32_t *__restrict__ out, const uint8_t *__restrict__ pad) {
+    const uint32_t lane = threadIdx.x & 63u, li = lane & 31u, g = lane >> 5;
+    const uint32_t t = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t wv = blockDim.x >> 6;
+    const uint64_t cg = n / 2 / ((uint64_t)gridDim.x * wv);
+    const K1Walk wk = k1_walk((K1Order)ORD, SCR, blockIdx.x, t, gridDim.x, wv, cg);
+    constexpr uint64_t kNone = ~0ull;
+    HalfX h0, h1, h2, h3;
+    auto ld = [&](HalfX &h, uint64_t gi, int q) {
+        // (past the walk's end: the table image, as K1 does; wave-uniform)
+        // (a uniform base and a 32-bit lane offset, as K1's ldh)
+        const uint8_t *wb = gi != kNone ? base + gi * 2 * kItemBytes : pad;
+        const uint32_t loff = g * (uint32_t)kItemBytes + li * 16u + 2048u * (uint32_t)q;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) h.v[k] = ld16_nt(wb + loff + k * 512);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto fold = [&](const HalfX &h) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x ^= h.v[k].x ^ h.v[k].y ^ h.v[k].z ^ h.v[k].w;
+        // (folded here: left alone the compiler sinks the XORs to the stores at
+        // the pass's end, and the ring's registers with them into scratch)
+        asm volatile("" : "+v"(x)::"memory");
+        return x;
+    };
+    auto even2 = [&](uint64_t a, uint64_t b) {
+        ld(h3, a, 1);
+        const uint32_t x = fold(h0);
+        ld(h0, b, 0);
+        return x ^ fold(h1);
+    };
+    auto odd2 = [&](uint64_t a, uint64_t b) {
+        ld(h1, a, 1);
+        const uint32_t x = fold(h2);
+        ld(h2, b, 0);
+        return x ^ fold(h3);
+    };
+    auto put = [&](uint32_t x, uint64_t gi) {
+        x = wave_xor32(x);
+        if (li == 0) out[gi * 2 + g] = x;
+    };
+    const uint64_t ss = wk.sstep;
+    uint64_t cur = wk.first;
+    ld(h0, cur, 0);
+    ld(h1, cur, 1);
+    ld(h2, cur + ss, 0);
+    for (uint64_t k = 0; k < cg; k += 4) {
+        const uint64_t nxt = k + 4 < cg ? cur + wk.pstep : kNone;
+        const uint32_t x0 = even2(cur + ss, cur + 2 * ss);
+        const uint32_t x1 = odd2(cur + 2 * ss, cur + 3 * ss);
+        const uint32_t x2 = even2(cur + 3 * ss, nxt);
+        const uint32_t x3 = odd2(nxt, nxt == kNone ? kNone : nxt + ss);
+        put(x0, cur), put(x1, cur + ss), put(x2, cur + 2 * ss), put(x3, cur + 3 * ss);
+        cur = nxt;
+        if (BAR) k1_round_barrier();
+    }
+}
+
+// k_fixed_body in a given order (the product's kernel around it: k_fixed).
+template <int ORD, bool SCR>
+__global__ __launch_bounds__(1024) void k_fixed_ord(const uint8_t *__restrict__ base, uint64_t stride, uint64_t nitems,
+                                                    const uint4 *__restrict__ img, uint32_t *__restrict__ out,
+                                                    K1Ctl *__restrict__ ctl) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    load_tables(smem, img, kLdsImageK1Bytes);
+    k_fixed_body<false, true, K1NoProbe, (K1Order)ORD, SCR>(base, stride, nitems, img, nullptr, out, blockDim.x, ctl,
+                                                            K1NoProbe{});
 }
 
 struct Pair {
@@ -177,12 +269,102 @@ float time_median(F launch, int reps) {
     return t[t.size() / 2];
 }
 
+// MODE order: the streams and K1 itself in every order, alternated.
+static int run_orders(int cus, int reps, uint64_t n, int rounds) {
+    const uint64_t W = (uint64_t)cus * 16, bytes = n * kItemBytes;
+    if (n == 0 || n % (8 * W)) {
+        fprintf(stderr, "ITEMS must be a multiple of %llu (whole passes for %llu waves)\n", (unsigned long long)(8 * W),
+                (unsigned long long)W);
+        return 2;
+    }
+    const uint64_t cg = n / 2 / W;
+    uint8_t *d;
+    uint32_t *out;
+    K1Ctl *dctl;
+    CHECK(hipMalloc(&d, bytes));
+    CHECK(hipMalloc(&out, n * 4));
+    CHECK(hipMalloc(&dctl, sizeof(K1Ctl)));
+    CHECK(hipMemset(dctl, 0, sizeof(K1Ctl)));
+    fill<<<4096, 256>>>((uint32_t *)d, bytes / 4);
+    std::vector<uint32_t> img(mcrc::kImageK1Dwords);
+    mcrc::build_lds_image_span(img.data(), 16);
+    uint4 *dimg;
+    CHECK(hipMalloc(&dimg, img.size() * 4));
+    CHECK(hipMemcpy(dimg, img.data(), img.size() * 4, hipMemcpyHostToDevice));
+    K1Ctl *ctl = cg >= kK1TailMinSteps ? dctl : nullptr;
+    printf("items %llu  %llu steps per wave  lockstep rounds %s  claimed tail %s  window orders %s\n", (unsigned long long)n,
+           (unsigned long long)cg, k1_rounds(cg, kK1RoundSteps) ? "on" : "off", ctl ? "on" : "off",
+           k1_order_for(kK1OrderWindowPass, cg) == kK1OrderWindowPass ? "run" : "fall back to ranges");
+    struct Mode {
+        const char *name;
+        const void *fn;
+        bool k1;
+    };
+    const Mode modes[] = {
+        {"ord ranges", (const void *)ord_ring<0, true, false>, false},
+        {"ord ranges bar", (const void *)ord_ring<0, true, true>, false},
+        {"ord pass+s", (const void *)ord_ring<2, true, false>, false},
+        {"ord pass+s bar", (const void *)ord_ring<2, true, true>, false},
+        {"ord pass+u bar", (const void *)ord_ring<2, false, true>, false},
+        {"ord step+s bar", (const void *)ord_ring<1, true, true>, false},
+        {"ord step+u bar", (const void *)ord_ring<1, false, true>, false},
+        {"K1 ranges", (const void *)k_fixed_ord<0, true>, true},
+        {"K1 pass+s", (const void *)k_fixed_ord<2, true>, true},
+        {"K1 pass+u", (const void *)k_fixed_ord<2, false>, true},
+        {"K1 step+s", (const void *)k_fixed_ord<1, true>, true},
+        {"K1 step+u", (const void *)k_fixed_ord<1, false>, true},
+    };
+    for (const Mode &m : modes)
+        CHECK(hipFuncSetAttribute(m.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsImageK1Bytes));
+    const uint64_t stride = kItemBytes;
+    auto launch = [&](const Mode &m) {
+        // (the streams take K1's 160 KiB of LDS too: one workgroup per CU)
+        if (m.k1) {
+            void *args[] = {(void *)&d, (void *)&stride, (void *)&n, (void *)&dimg, (void *)&out, (void *)&ctl};
+            CHECK(hipLaunchKernel(m.fn, dim3(cus), dim3(1024), args, kLdsImageK1Bytes, 0));
+        } else {
+            void *args[] = {(void *)&d, (void *)&n, (void *)&out, (void *)&dimg};
+            CHECK(hipLaunchKernel(m.fn, dim3(cus), dim3(1024), args, kLdsImageK1Bytes, 0));
+        }
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    while (std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(300)) {
+        for (int i = 0; i < 20; ++i) launch(modes[7]);
+        CHECK(hipDeviceSynchronize());
+    }
+    std::vector<uint32_t> ref[2], h(n);
+    int bad = 0;
+    for (int round = 0; round < rounds; ++round) {
+        printf("-- round %d\n", round);
+        for (const Mode &m : modes) {
+            CHECK(hipMemset(out, 0, n * 4));
+            const float ms = time_median([&] { launch(m); }, reps);
+            CHECK(hipMemcpy(h.data(), out, n * 4, hipMemcpyDeviceToHost));
+            std::vector<uint32_t> &r = ref[m.k1];
+            if (r.empty()) r = h;
+            const bool same = memcmp(h.data(), r.data(), n * 4) == 0;
+            bad += !same;
+            printf("%-18s %.4f ms  %7.1f GB/s  %5.1f %% of 8 TB/s  %s\n", m.name, ms, bytes / (ms * 1e-3) / 1e9,
+                   bytes / (ms * 1e-3) / 8e12 * 100,
+                   same ? (m.k1 ? "crc = ranges" : "xor = ranges") : (m.k1 ? "CRC MISMATCH" : "XOR MISMATCH"));
+            fflush(stdout);
+        }
+    }
+    CHECK(hipFree(d));
+    CHECK(hipFree(out));
+    CHECK(hipFree(dctl));
+    CHECK(hipFree(dimg));
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     const int reps = argc > 1 ? atoi(argv[1]) : 30;
     hipDeviceProp_t p;
     CHECK(hipGetDeviceProperties(&p, 0));
     const int cus = p.multiProcessorCount;
     printf("device %s  CUs %d  reps %d\n", p.gcnArchName, cus, reps);
+    if (argc <= 2 || strcmp(argv[2], "waves") != 0)
+        return run_orders(cus, reps, argc > 3 ? strtoull(argv[3], nullptr, 0) : kItems, argc > 4 ? atoi(argv[4]) : 5);
     const uint64_t bytes = kItems * kItemBytes;
     uint8_t *d;
     uint32_t *out;
@@ -198,7 +380,7 @@ int main(int argc, char **argv) {
                               kLdsImageK1Bytes));
     auto run_k1 = [&](int threads) {
         hipLaunchKernelGGL((k_fixed<false, true>), dim3(cus), dim3(threads), kLdsImageK1Bytes, 0, d, kItemBytes, kItems,
-                           dimg, nullptr, out);
+                           dimg, nullptr, out, (K1Ctl *)nullptr);
     };
     if (reps > 1) {
         const auto t0 = std::chrono::steady_clock::now();
