@@ -28,6 +28,12 @@
  *                          the page staged once, the walk's lists kept on the
  *                          device, one merged list with each image's kind and
  *                          ITEM_ntotal for a single rescue loop.
+ *   crc32c_repair_items    the images those calls prove damaged (kind 0,
+ *                          CRC32C_ITEM_DAMAGED, badcrc_from_extstore) and the
+ *                          reference drops: where one inverted bit explains the
+ *                          mismatch, the stored CRC names it; it is flipped back
+ *                          and the image proven again.  crc32c_locate_bit is the
+ *                          same search for one span on the host (no GPU).
  *   crc32c_verify_items    the read-verify compare of storage.c:159-178 applied
  *                          to every item image of a packed extstore page
  *                          (walk of storage.c:950-960): CRC over
@@ -73,7 +79,7 @@ extern "C" {
                               passes disagreed on some wbuf (an internal invariant;
                               the results are not valid) */
 #define CRC32C_EWORK (-7)  /* crc32c_salvage_pages / _recover_pages: the candidates' spans exceed
-                              the work bound */
+                              the work bound; crc32c_repair_items: the damaged images' spans do */
 
 /* flags */
 #define CRC32C_DEVICE 0x1u    /* every pointer in the batch is device memory of the
@@ -90,6 +96,7 @@ extern "C" {
                                  carries its CRC (compaction copies images with it,
                                  storage.c:1004-1006): it is verified against that
                                  value and not written; see crc32c_stamp_items */
+#define CRC32C_LOCATE_ONLY 0x20u /* repair calls: report, write nothing into the buffer */
 
 /* ok[] values of the stamp calls (0: malformed, or a carried image whose stored
  * CRC does not match) */
@@ -319,6 +326,101 @@ int crc32c_recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_by
                          uint64_t *nsalvaged, uint64_t *scanned, uint64_t *ncand, unsigned flags,
                          void *stream);
 
+/* Correct single-bit damage from the stored CRC.  An image whose own bytes were
+ * hit comes back as kind 0 from the walk, as CRC32C_ITEM_DAMAGED from
+ * crc32c_copy_items, as badcrc_from_extstore on the read path, and is dropped.
+ * When exactly one bit of it is inverted, the bits that say which one are still
+ * in it: this call finds the bit, inverts it again and so proves the image.
+ *
+ * The rule, per image at o = item_offsets[i].  The image is judged sane exactly
+ * as crc32c_verify_items judges it (region_bytes and CRC32C_CFLAGS64 apply).
+ * nt = ITEM_ntotal, L = nt - 32, c = crc32c(0, base + o + 32, L), e = the
+ * little-endian dword at o + 28, S = c ^ e.
+ *   not sane, or L > max_span   ok = 0, bit = CRC32C_NO_BIT, nothing written.
+ *                               max_span == 0 means CRC32C_REPAIR_SPAN_DEFAULT;
+ *                               max_span > CRC32C_REPAIR_SPAN_MAX: CRC32C_EINVAL.
+ *   S == 0                      ok = 1, bit = CRC32C_NO_BIT.
+ *   otherwise                   the positions are the image's bits k in
+ *     [224, 8 nt): bit k % 8 (LSB = 0) of image byte k / 8 -- the stored CRC and
+ *     every byte it covers.  k is located when the image with bit k inverted
+ *     has a stored CRC equal to its computed one.  In syndrome form: g(0) =
+ *     0x80000000, g(t + 1) = (g(t) >> 1) ^ (g(t) & 1 ? 0x82F63B78 : 0);
+ *     stored-CRC bit j (k = 224 + j) has t = 31 - j, bit b of span byte m (k =
+ *     256 + 8 m + b) has t = 32 + 8 (L - 1 - m) + (7 - b); k is located iff
+ *     g(t) == S.  At most one k exists.
+ *     A located k is accepted when (1) it is not a length-determining header
+ *     bit -- nbytes (bytes 32..35), nkey (byte 41), it_flags bits 1 and 8 (byte
+ *     38 bit 1, byte 39 bit 0): inverting one changes nt, so the image would not
+ *     verify over its own span -- and (2) with the bit inverted nbytes >= 2 and
+ *     the image's last two bytes are "\r\n" (crc32c_salvage_pages' candidate
+ *     rule).
+ *     accepted                  ok = CRC32C_ITEM_REPAIRED, bit = k; without
+ *                               CRC32C_LOCATE_ONLY that one bit of the buffer
+ *                               is inverted, so the image then passes
+ *                               crc32c_verify_items.
+ *     not located / accepted    ok = 0, bit = CRC32C_NO_BIT, nothing written.
+ * *nrepaired counts ok == CRC32C_ITEM_REPAIRED and *nbad counts ok == 0; both are
+ * always filled.  ok and bit hold n entries.
+ *
+ * What the rule guarantees, and why.  A register holds a polynomial mod
+ * P = 0x11EDC6F41 (reflected: 0x80000000 is 1, g(t) = x^t).  The stored CRC
+ * followed by the span is a codeword exactly when S == 0, S is linear in the
+ * codeword's bits, and inverting the bit with exponent t alone gives S = x^t.
+ *   - P has 18 terms, so x + 1 divides it and every codeword has even weight:
+ *     an error pattern of even weight has S divisible by x + 1, a power of x
+ *     never is.  Damage of any even number of bits inside [o + 28, o + nt) is
+ *     therefore never "repaired".
+ *   - x has order 2^31 - 1 mod P (x^(2^31 - 1) = 1 and 2^31 - 1 is prime), and a
+ *     codeword of L <= CRC32C_REPAIR_SPAN_MAX bytes has 32 + 8 L < 2^31 - 1
+ *     positions: their x^t are distinct.  One inverted bit there is always
+ *     located, at its own position and no other, and accepted unless it is a
+ *     length bit.
+ *   - Damage of any other kind (three or more bits, a wrong length) leaves an S
+ *     that is as good as random: it is taken for a single bit with probability
+ *     about (8 nt - 224) / 2^32 per damaged image -- 2^-17 (8e-6) for a 4 KiB
+ *     image, 2^-9 (2e-3) for a 1 MiB one, 2^-8 at the default max_span.  The
+ *     CRLF test multiplies that by 2^-16 only where the damage moved the
+ *     image's end.  The caller chooses max_span with that in mind.
+ * A repaired image is thus weaker evidence than an intact one: a separate,
+ * explicit call, not a mode of the verify.
+ *
+ * The work bound.  The list is expected to name distinct, disjoint images, as
+ * the walk's lists do.  If the spans of the images with S != 0 and L <= max_span
+ * add up to more than base_bytes (disjoint images cannot), the call returns
+ * CRC32C_EWORK: nothing is written into the buffer, ok and bit are unspecified,
+ * *nrepaired = 0.  An offset listed twice below that bound leaves that one
+ * image's content unspecified and touches nothing else.
+ *
+ * With CRC32C_DEVICE base, item_offsets, ok and bit are device memory and the
+ * call runs on `stream`; the two counts are host words, read back, so
+ * CRC32C_ASYNC has no effect.  Without it everything is host memory: the buffer
+ * is staged as crc32c_verify_items stages it and the host inverts the located
+ * bits in the caller's buffer.  CRC32C_EINVAL: NULL base, item_offsets, ok, bit,
+ * nrepaired or nbad.  n == 0: CRC32C_OK with zero counts; no device:
+ * CRC32C_ENODEV, nothing written.  No byte outside [base, base + base_bytes) is
+ * read beyond what crc32c_verify_items reads; nothing but the outputs and the
+ * accepted bits is written.  After the call crc32c_last_kernel_ms() is the time
+ * of the search kernel alone (0 when no image had S != 0).  Scratch
+ * (grow-only): 20 B per image beside crc32c_verify_items' own (a host call 17 B
+ * more and the staged buffer), 32 B per image with S != 0. */
+#define CRC32C_ITEM_REPAIRED 5 /* ok[]: one bit located (and, without CRC32C_LOCATE_ONLY, flipped back) */
+#define CRC32C_NO_BIT UINT64_MAX
+#define CRC32C_REPAIR_SPAN_DEFAULT 0x200000u /* 2 MiB */
+#define CRC32C_REPAIR_SPAN_MAX 0x0fffffc0u   /* 32 + 8 L < 2^31 - 1: the located position is unique */
+int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes,
+                        const uint64_t *item_offsets, uint64_t n, uint32_t max_span,
+                        uint8_t *ok, uint64_t *bit, uint64_t *nrepaired, uint64_t *nbad,
+                        unsigned flags, void *stream);
+
+/* The same search for one span on the host, no GPU: after a scalar mismatch of
+ * a read (storage.c:172-178, io_depth 1).  crc_computed = crc32c(0, span, len),
+ * crc_stored what the item carries.  Returns q < 32 for bit q of the stored CRC
+ * and q >= 32 for bit (q - 32) % 8 of span byte (q - 32) / 8; CRC32C_NO_BIT when
+ * the two CRCs are equal, when no position of a len-byte span explains them, or
+ * when len > CRC32C_REPAIR_SPAN_MAX.  For an item image k = 224 + q; the
+ * length-bit and CRLF conditions are the caller's.  4 + len table steps. */
+uint64_t crc32c_locate_bit(uint32_t crc_computed, uint32_t crc_stored, uint64_t len);
+
 /* Stamp the spill CRC of n item images (storage.c:567, gathered per wbuf
  * before it is submitted): exptime (bytes 28..31) of image i receives
  * crc32c(0, image + 32, ITEM_ntotal - 32).  Host or device per flags; with
@@ -473,7 +575,7 @@ const char *crc32c_strerror(int err);
 /* Duration of this thread's last synchronous device batch (milliseconds,
  * hipEvent-measured on its stream); -1 before the first one.  After
  * crc32c_salvage_pages and crc32c_recover_pages: the scan's counting pass over
- * the eligible bytes. */
+ * the eligible bytes.  After crc32c_repair_items: the search kernel. */
 float crc32c_last_kernel_ms(void);
 
 #ifdef __cplusplus

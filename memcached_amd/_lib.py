@@ -27,11 +27,16 @@ CRC32C_DEVICE = 0x1
 CRC32C_ASYNC = 0x2
 CRC32C_CFLAGS64 = 0x8
 CRC32C_KEEP_STAMPED = 0x10
+CRC32C_LOCATE_ONLY = 0x20  # repair calls: report, write nothing into the buffer
 CRC32C_ITEM_STAMPED = 1  # ok[] values of the stamp calls
 CRC32C_ITEM_KEPT = 2
 CRC32C_ITEM_COPIED = 1  # ok[] values of crc32c_copy_items
 CRC32C_ITEM_DAMAGED = 3
 CRC32C_ITEM_SALVAGED = 4  # kind[] of crc32c_recover_pages: found by the salvage (0 / 1: the walk's verdicts)
+CRC32C_ITEM_REPAIRED = 5  # ok[] of crc32c_repair_items: one bit located (and flipped back)
+CRC32C_NO_BIT = 2**64 - 1  # bit[] of crc32c_repair_items / crc32c_locate_bit: no position
+CRC32C_REPAIR_SPAN_DEFAULT = 0x200000  # crc32c_repair_items' max_span when 0 is passed
+CRC32C_REPAIR_SPAN_MAX = 0x0FFFFFC0  # the longest span whose located position is unique
 CRC32C_MAX_SPAN = 0x7FFF0000  # longest span (include/crc32c_batch.h)
 CRC32C_SALVAGE_WORK_MAX = 64  # crc32c_salvage_pages' work bound: candidates' spans per scanned byte
 
@@ -43,7 +48,7 @@ EXPORTED = (
     "crc32c_batch_submit", "crc32c_batch_wait", "crc32c_strerror", "crc32c_last_kernel_ms",
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
-    "crc32c_set_k1_tail_min", "crc32c_recover_pages",
+    "crc32c_set_k1_tail_min", "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit",
 )
 
 
@@ -92,6 +97,8 @@ PROTOTYPES = {
                                     _PTR]),
     "crc32c_recover_pages": (_INT, [_PTR, _U64, _U64, _PTR, _PTR, _PTR, _U64, _U64P, _U64P, _U64P, _U64P, _U64P, _UINT,
                                     _PTR]),
+    "crc32c_repair_items": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _U32, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
+    "crc32c_locate_bit": (_U64, [_U32, _U32, _U64]),
     "crc32c_batch_chains": (_INT, [_SPANS, _PTR, _U64, _PTR, _UINT, _PTR]),
     "crc32c_host_alloc": (_PTR, [_SIZE]),
     "crc32c_host_free": (None, [_PTR]),
@@ -108,7 +115,7 @@ PROTOTYPES = {
 }
 # what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
 NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min",
-         "crc32c_recover_pages")
+         "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit")
 
 
 def _load():

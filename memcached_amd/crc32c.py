@@ -13,6 +13,8 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``verify_pages`` walk + verify whole pages on the device (storage.c:950-1070)
 * ``salvage_pages`` the intact images behind a header that ended a wbuf's walk
 * ``recover_pages`` verify_pages + salvage_pages in one call, one merged list
+* ``repair_items`` single-bit damage of item images located by the stored CRC and flipped back
+  (``locate_bit``: the same search for one span on the host)
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
 
@@ -31,7 +33,8 @@ import numpy as np
 from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
-# (recover_pages is public as well; tests/test_python_face.py pins this list as it stood before it)
+# (recover_pages, repair_items and locate_bit are public as well; tests/test_python_face.py pins this list as it
+# stood before them)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
            "batch_multi",
@@ -453,6 +456,44 @@ def recover_pages(buf, wbuf_bytes, stream=None, cflags64=False):
     info = dict(zip(("nbad", "nsalvaged", "scanned", "ncand"), (int(c.value) for c in counts[1:])))
     _check_carrying(status[0], "crc32c_recover_pages", _lib.CRC32C_EWORK, offsets=offs, lens=lens, kind=kind, **info)
     return offs, lens, kind, info
+
+
+def repair_items(buf, item_offsets, region_bytes=0, max_span=0, locate_only=False, stream=None, cflags64=False):
+    """Correct single-bit damage of item images from their stored CRC
+    (crc32c_repair_items): for every image whose stored CRC does not match,
+    the one bit of its stored CRC or span whose inversion explains the
+    mismatch is looked for; when it exists, is no length-determining header bit
+    and leaves the value ending in CRLF, it is inverted again in ``buf``.
+
+    Returns (ok, bit, {"nrepaired", "nbad"}) for numpy and torch buffers: ok[i]
+    is 1 for an intact image, CRC32C_ITEM_REPAIRED (5) for a repaired one with
+    bit[i] the image's bit index (bit k % 8 of image byte k // 8), else 0 with
+    bit[i] = CRC32C_NO_BIT (not sane, longer than ``max_span`` -- 0: 2 MiB --
+    or not explained by one bit).  ``locate_only``: the same verdicts, ``buf``
+    is left as it is; a host buffer that is not a writable contiguous uint8
+    numpy array is accepted only so.  ``region_bytes`` and ``cflags64`` as for
+    verify_items.  Raises Crc32cError(CRC32C_EWORK) when the damaged images'
+    spans add up to more than the buffer (a list of overlapping images)."""
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf, inplace=None if locate_only else
+                              "repair_items needs {} (repaired in place) unless locate_only is set")
+    offs = side.desc(item_offsets, "item_offsets", _U64)
+    n = _count(offs)
+    ok, bit = side.empty(n, _U8), side.empty(n, _U64)
+    nrepaired, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    flags = side.flag | _flags(cflags64) | (_lib.CRC32C_LOCATE_ONLY if locate_only else 0)
+    check(lib.crc32c_repair_items(_ptr(buf), nbytes, region_bytes, _ptr(offs), n, max_span, _ptr(ok), _ptr(bit),
+                                  ctypes.byref(nrepaired), ctypes.byref(nbad), flags, side.stream),
+          "crc32c_repair_items")
+    return ok, bit, {"nrepaired": int(nrepaired.value), "nbad": int(nbad.value)}
+
+
+def locate_bit(crc_computed: int, crc_stored: int, length: int) -> int:
+    """crc32c_locate_bit, on the host: the one position of a ``length``-byte
+    span or of its stored CRC whose inversion turns ``crc_stored`` into a match
+    for ``crc_computed`` -- q < 32: bit q of the stored CRC; else bit (q - 32) %
+    8 of span byte (q - 32) // 8 -- or CRC32C_NO_BIT."""
+    return int(lib.crc32c_locate_bit(crc_computed & 0xFFFFFFFF, crc_stored & 0xFFFFFFFF, length))
 
 
 def batch_chains(buf, offsets, lens, chain_first, stream=None):

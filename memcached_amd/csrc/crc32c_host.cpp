@@ -7,6 +7,7 @@
 
 #include "../../include/crc32c_batch.h"
 #include "crc32c_gf2.h"
+#include "repair_geom.h"
 
 #if defined(__x86_64__)
 #include <cpuid.h>
@@ -214,3 +215,19 @@ bool item_sane(const uint8_t *base, uint64_t base_bytes, uint64_t region, uint64
 }
 
 }  // namespace mcrc
+
+// crc32c_locate_bit (crc32c_batch.h): the search of crc32c_repair_items for one
+// span, a byte of positions a step (repair_geom.h).  The byte table of x^-8 is
+// built on the stack per call: 2 K bit steps, against 4 + len byte steps.
+extern "C" uint64_t crc32c_locate_bit(uint32_t crc_computed, uint32_t crc_stored, uint64_t len) {
+    uint32_t v = crc_computed ^ crc_stored;
+    if (v == 0 || len > mcrc::kRepairSpanMax) return CRC32C_NO_BIT;
+    uint32_t inv8[256];
+    for (uint32_t b = 0; b < 256; ++b) inv8[b] = mcrc::repair_unstep8(b << 24);
+    const uint64_t steps = mcrc::repair_steps(len);
+    for (uint64_t j = 0; j < steps; ++j) {
+        if (mcrc::repair_hit(v)) return mcrc::repair_q_of_t(8 * j + mcrc::repair_hit_r(v), len);
+        v = (v << 8) ^ inv8[v >> 24];
+    }
+    return CRC32C_NO_BIT;
+}

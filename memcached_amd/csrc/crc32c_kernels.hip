@@ -41,3 +41,4 @@
 #include "k_walk.h"    // k_gather_offs, k_scatter_ok, k_chain, k_walk
 #include "k_salvage.h" // crc32c_salvage_pages: k_salvage_regions, k_salvage_scan, k_salvage_pick
 #include "k_recover.h" // crc32c_recover_pages: k_recover_regions, k_recover_merge
+#include "k_repair.h"  // crc32c_repair_items: k_repair_count, k_repair_emit, k_repair_search, k_repair_apply

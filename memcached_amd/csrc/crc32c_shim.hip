@@ -60,6 +60,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_walk.h"
 #include "shim_salvage.h"
 #include "shim_recover.h"
+#include "shim_repair.h"
 
 // Batch C ABI
 extern "C" {
@@ -111,7 +112,7 @@ const char *crc32c_strerror(int err) {
         case CRC32C_ENOMEM: return "out of device or pinned memory";
         case CRC32C_ERANGE: return "span outside [base, base + base_bytes) (not read)";
         case CRC32C_EWALK: return "device page walk passes disagreed (results not valid)";
-        case CRC32C_EWORK: return "salvage candidates' spans exceed the work bound (nothing verified)";
+        case CRC32C_EWORK: return "the candidates' or damaged images' spans exceed the work bound (nothing verified)";
         default: return "unknown error";
     }
 }
@@ -343,6 +344,13 @@ int crc32c_recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_by
                          uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
     return recover_pages(base, base_bytes, wbuf_bytes, offsets, lens, kind, cap, nitems, nbad, nsalvaged, scanned,
                          ncand, flags, stream);
+}
+
+int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets,
+                        uint64_t n, uint32_t max_span, uint8_t *ok, uint64_t *bit, uint64_t *nrepaired, uint64_t *nbad,
+                        unsigned flags, void *stream) {
+    return repair_items(base, base_bytes, region_bytes, item_offsets, n, max_span, ok, bit, nrepaired, nbad, flags,
+                        stream);
 }
 
 int crc32c_shard_cuts(const uint32_t *lens, uint32_t len, uint64_t n, int parts, uint64_t *cuts) {

@@ -136,6 +136,16 @@ struct Device {
     DevBuf<uint32_t> rc_cnt, rc_pre, rc_lens;
     DevBuf<uint64_t> rc_slots, rc_offs;
     DevBuf<uint8_t> rc_kind;
+    // crc32c_repair_items: per image its CRC, the two counts and their scans; per
+    // listed image its record, first chunk and located t; the counters and
+    // their pinned twin; a host call's verdicts and positions
+    DevBuf<uint32_t> rp_crc, rp_lcnt, rp_ccnt, rp_lpre, rp_cpre, rp_first, rp_found;
+    DevBuf<mcrc_dev::RepairRec> rp_recs;
+    DevBuf<unsigned long long> rp_ctr;
+    PinBuf<unsigned long long> rp_host;
+    DevBuf<uint8_t> rp_ok;
+    DevBuf<uint64_t> rp_bit;
+    PinBuf<uint64_t> rp_hbit;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

@@ -1,0 +1,140 @@
+// shim_repair.h -- repair_items, the body of crc32c_repair_items: the images'
+// CRCs through the item runners (run_items<2> with the CRCs sent to scratch:
+// k_small or the planned path, the routes that honour SpanArgs::out), the
+// listing of the images whose stored CRC differs, the search for the bit that
+// explains each difference and the verdicts (k_repair.h; the contract:
+// include/crc32c_batch.h), under one lock and one lease.  One read-back sizes
+// the search: the listed images, their chunks and their spans' sum for the work
+// bound, so a clean list costs the CRCs plus one count.  A host buffer is
+// staged as crc32c_verify_items stages a large one, verdicts and positions come
+// back through scratch, and the host inverts the accepted bits in the caller's
+// buffer.
+// Scratch (grow-only): per image 4 B of CRC, 8 B of counts and 8 B of their
+// scans (a host call: 8 B of offset, 1 B of verdict and 8 B of position more,
+// and the staged buffer); per listed image a 24-B record, 4 B of first chunk
+// and 4 B of located position.
+#pragma once
+
+namespace {
+
+static_assert(mcrc_dev::kItemRepaired == CRC32C_ITEM_REPAIRED, "the verdict the kernels write is the header's");
+static_assert(mcrc::kRepairSpanMax == CRC32C_REPAIR_SPAN_MAX && mcrc::kRepairSpanDefault == CRC32C_REPAIR_SPAN_DEFAULT &&
+                  mcrc::kRepairNoBit == CRC32C_NO_BIT,
+              "repair_geom.h restates the header's constants");
+static_assert(32 + 8 * (uint64_t)CRC32C_REPAIR_SPAN_MAX < mcrc::kRepairOrder, "a located position is unique");
+
+int repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets, uint64_t n,
+                 uint32_t max_span, uint8_t *ok, uint64_t *bit, uint64_t *nrepaired, uint64_t *nbad, unsigned flags,
+                 void *stream) {
+    if (!base || !item_offsets || !ok || !bit || !nrepaired || !nbad || max_span > CRC32C_REPAIR_SPAN_MAX)
+        return CRC32C_EINVAL;
+    Device *dp = nullptr;
+    int rc = current_device(&dp);
+    if (rc) return rc;
+    Device &d = *dp;
+    *nrepaired = *nbad = 0;
+    if (n == 0) return CRC32C_OK;
+    const bool dev = flags & CRC32C_DEVICE, locate_only = flags & CRC32C_LOCATE_ONLY;
+    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
+    // (k_small, or the planned path: K5's stamps go into the images themselves)
+    const mcrc::ItemRoute route = mcrc::item_route(n, base_bytes, small_max(), false);
+    if (route == mcrc::ItemRoute::invalid) return CRC32C_EINVAL;
+    std::lock_guard<std::mutex> lk(d.mu);
+    hipStream_t st = dev ? (hipStream_t)stream : d.stream;  // (device: NULL is the default stream)
+    if (!dev) HIP_OK(hipSetDevice(d.id));
+    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
+
+    mcrc_dev::SpanArgs a = item_args(d, base, base_bytes, region_bytes, n, flags);
+    a.offsets = item_offsets;
+    mcrc_dev::RepairArgs r{};
+    r.max_span = max_span ? max_span : CRC32C_REPAIR_SPAN_DEFAULT;
+    r.ok = ok;
+    r.bit = bit;
+    uint32_t *const crc = d.rp_crc.reserve(n * 4);
+    r.lcnt = d.rp_lcnt.reserve(n * 4);
+    r.ccnt = d.rp_ccnt.reserve(n * 4);
+    uint32_t *const lpre = d.rp_lpre.reserve((n + 1) * 4), *const cpre = d.rp_cpre.reserve((n + 1) * 4);
+    r.ctr = d.rp_ctr.reserve(mcrc_dev::kRpWords * sizeof(unsigned long long));
+    unsigned long long *const h = d.rp_host.reserve((mcrc_dev::kRpWords + 1) * sizeof(unsigned long long));
+    if (!crc || !r.lcnt || !r.ccnt || !lpre || !cpre || !r.ctr || !h) return CRC32C_ENOMEM;
+    r.crc = crc;
+    uint32_t *const h32 = (uint32_t *)(h + mcrc_dev::kRpWords);  // the two scans' totals
+    if (!dev) {
+        uint8_t *b = d.stage.reserve(base_bytes);
+        uint64_t *o = d.item_offs.reserve(n * 8);
+        r.ok = d.rp_ok.reserve(n);
+        r.bit = d.rp_bit.reserve(n * 8);
+        if (!b || !o || !r.ok || !r.bit || !d.pin_ok.reserve(n) || !d.rp_hbit.reserve(n * 8)) return CRC32C_ENOMEM;
+        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(o, item_offsets, n * 8, hipMemcpyHostToDevice, st));
+        a.base = b;
+        a.offsets = o;
+    }
+
+    // the images' CRCs, into scratch
+    mcrc_dev::SpanArgs c = a;
+    c.out = crc;
+    c.ok = nullptr;
+    Count count = nullptr;
+    if ((rc = run_items<2>(d, c, route, st, &count))) return rc;
+
+    // the verdicts that need no search, the listed images and the work bound's sum
+    const unsigned grid = (unsigned)mcrc::count_grid(n);
+    HIP_OK(hipMemsetAsync(r.ctr, 0, mcrc_dev::kRpWords * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(mcrc_dev::k_repair_count, dim3(grid), dim3(256), 0, st, a, r);
+    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)r.lcnt, n, lpre);
+    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)r.ccnt, n, cpre);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h, r.ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h32, lpre + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h32 + 1, cpre + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    g_last_kernel_ms = 0.0f;  // (no search ran yet: not the time of an earlier call)
+    const uint64_t nl = h32[0], work = h[mcrc_dev::kRpWork];
+    // (the chunks' 32-bit sum is exact below the bound: a chunk per kRepairChunk bytes of span and one per image)
+    if (work > base_bytes || work / mcrc::kRepairChunk + 2 * nl >= mcrc::kCountMax) return CRC32C_EWORK;
+    const uint64_t nchunks = h32[1];
+
+    if (nl) {
+        mcrc_dev::RepairRec *const recs = d.rp_recs.reserve(nl * sizeof(mcrc_dev::RepairRec));
+        uint32_t *const first = d.rp_first.reserve(nl * 4), *const found = d.rp_found.reserve(nl * 4);
+        if (!recs || !first || !found) return CRC32C_ENOMEM;
+        hipLaunchKernelGGL(mcrc_dev::k_repair_emit, dim3(grid), dim3(256), 0, st, a, r, (const uint32_t *)lpre,
+                           (const uint32_t *)cpre, recs, first, found, nl);
+        // a lane per chunk, eight workgroups per CU at the most
+        const uint64_t sgrid = std::min<uint64_t>((nchunks + 255) / 256, (uint64_t)std::max(d.cus, 1) * 8);
+        HIP_OK(hipEventRecord(d.ev0, st));
+        hipLaunchKernelGGL(mcrc_dev::k_repair_search, dim3((unsigned)sgrid), dim3(256), 0, st,
+                           (const mcrc_dev::RepairRec *)recs, (const uint32_t *)first, nl, nchunks,
+                           (const uint32_t *)d.xpow, found);
+        HIP_OK(hipEventRecord(d.ev1, st));
+        // (a staged buffer is the call's own copy: the host inverts the caller's bits)
+        hipLaunchKernelGGL(mcrc_dev::k_repair_apply, dim3((unsigned)mcrc::final_grid(nl)), dim3(256), 0, st, a, r,
+                           (const mcrc_dev::RepairRec *)recs, (const uint32_t *)found, nl,
+                           (uint32_t)(locate_only || !dev));
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipMemcpyAsync(h + mcrc_dev::kRpBad, r.ctr + mcrc_dev::kRpBad, 2 * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, st));
+    uint8_t *const h_ok = d.pin_ok.get();
+    uint64_t *const h_bit = d.rp_hbit.get();
+    if (!dev) {
+        HIP_OK(hipMemcpyAsync(h_ok, r.ok, n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_bit, r.bit, n * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    if (nl) (void)hipEventElapsedTime(&g_last_kernel_ms, d.ev0, d.ev1);  // (crc32c_last_kernel_ms: the search)
+    if (!dev) {
+        memcpy(ok, h_ok, n);
+        memcpy(bit, h_bit, n * 8);
+        if (!locate_only)
+            for (uint64_t i = 0; i < n; ++i)
+                if (ok[i] == CRC32C_ITEM_REPAIRED)
+                    ((uint8_t *)base)[item_offsets[i] + bit[i] / 8] ^= (uint8_t)(1u << (bit[i] % 8));
+    }
+    *nbad = h[mcrc_dev::kRpBad];
+    *nrepaired = h[mcrc_dev::kRpRepaired];
+    return CRC32C_OK;
+}
+
+}  // namespace
