@@ -11,6 +11,9 @@ from memcached_amd import _lib
 from memcached_amd import crc32c as mc
 from tests import repair_model as rm
 from tests import salvage_cases as sc
+from tests.repair_cases import flip as _flip
+from tests.repair_cases import mixed as _mixed
+from tests.repair_cases import place as _place
 
 pytestmark = pytest.mark.gpu
 NO_BIT, REPAIRED = rm.NO_BIT, rm.REPAIRED
@@ -58,23 +61,6 @@ def _check(buf, offs, small=(None,), region=0, cfl=4, max_span=0, locate_only=Fa
             if prev is not None:
                 mc.set_small_max(prev)
     return ok, bit
-
-
-def _flip(buf, o, k):
-    buf[o + k // 8] ^= 1 << (k % 8)
-
-
-def _place(images, align=1, lead=0):
-    """(buffer, offsets): the images packed, each start rounded up to align, + lead."""
-    offs, o = [], 0
-    for img in images:
-        o = -(-o // align) * align + lead
-        offs.append(o)
-        o += len(img)
-    buf = np.zeros(o + 64, np.uint8)
-    for at, img in zip(offs, images):
-        buf[at:at + len(img)] = np.frombuffer(bytes(img), np.uint8)
-    return buf, np.array(offs, np.uint64)
 
 
 def test_every_position_of_a_52_byte_image_at_every_alignment():
@@ -152,34 +138,6 @@ def test_one_long_image():
     # over max_span: left alone
     ok, bit = _check(buf, offs[:2], max_span=1 << 20)
     assert ok.tolist() == [0, 0]
-
-
-def _mixed(rng, n, max_span):
-    """n small images in one buffer, damaged by class, two long ones among them."""
-    images = [sc.image_nt(rng, int(rng.integers(60, 200)), cas=bool(i & 1)) for i in range(n)]
-    images[n // 3] = sc.image_nt(rng, max_span + 32 + 1)  # one byte over max_span
-    images[n // 2] = sc.image_nt(rng, max_span + 32)      # just within
-    buf, offs = _place(images)
-    kinds = []
-    for i, (o, img) in enumerate(zip(offs.tolist(), images)):
-        nt, c = len(img), i % 10
-        if i in (n // 3, n // 2) or c in (3, 9):  # one bit
-            k = int(rng.integers(224, 8 * nt))
-            while rm.length_bit(k):
-                k = int(rng.integers(224, 8 * nt))
-            _flip(buf, o, k)
-        elif c in (4, 5):  # two bits, three bits
-            for k in rng.choice(np.arange(224, 8 * nt), 2 + (c == 5), replace=False).tolist():
-                _flip(buf, o, int(k))
-        elif c == 6:  # outside what the CRC covers
-            _flip(buf, o, int(rng.integers(0, 224)))
-        elif c == 7:  # a length bit
-            _flip(buf, o, [8 * 32 + int(rng.integers(0, 32)), 8 * 41 + int(rng.integers(0, 8)), 8 * 38 + 1,
-                           8 * 39][int(rng.integers(0, 4))])
-        elif c == 8:  # not sane
-            buf[o + 41] = 0
-        kinds.append(c)
-    return buf, offs, np.array(kinds)
 
 
 def test_mixed_list_of_ten_thousand():

@@ -5,7 +5,6 @@ small-batch limit and compared exactly -- every CRC, every ok value, every
 byte, nbad and nitems -- with the oracle and the CPU models of
 tests/keep_stamped_model.py.  Nothing expected here comes from the library."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
@@ -15,15 +14,18 @@ try:  # GPU processes load torch (and its HIP runtime) before libmcrc32c.so
 except ImportError:
     pass
 
-from memcached_amd import _lib, layout
+from memcached_amd import _lib
 from memcached_amd import crc32c as mc
 
-from . import keep_stamped_model as model
 from . import oracle
+from .routes_cases import WBUF
+from .routes_cases import items_case as _items_case
+from .routes_cases import items_want as _items_want
+from .routes_cases import pages_case as _pages_case
+from .routes_cases import pages_want as _pages_want
+from .routes_cases import short_spans as _short_spans
 
 pytestmark = pytest.mark.gpu
-
-MiB = 1 << 20
 
 
 @pytest.fixture(scope="module")
@@ -39,18 +41,6 @@ def _dev(torch, arr):
 
 
 # -- spans ---------------------------------------------------------------------
-
-@functools.lru_cache(maxsize=None)
-def _short_spans():
-    """8193 spans of 1..300 B at unaligned offsets of a buffer under 8 MiB, and
-    their CRCs."""
-    rng = np.random.default_rng(811)
-    lens = rng.integers(1, 301, 8193).astype(np.uint32)
-    offs = (np.cumsum(lens + rng.integers(0, 40, 8193)) - lens + 3).astype(np.uint64)
-    buf = rng.integers(0, 256, int(offs[-1]) + 300 + 5, dtype=np.uint8)
-    assert buf.size <= 8 * MiB and len(set((offs % 16).tolist())) == 16
-    return buf, offs, lens, oracle.batch(buf, offs, lens)
-
 
 @pytest.mark.parametrize("n", [8192, 8193])
 def test_short_spans_small_and_planned(torch, n):
@@ -82,56 +72,6 @@ def test_fixed_length_edges(torch, length):
 
 # -- items ---------------------------------------------------------------------
 
-def _mixed(items, rng, pad_to=None, nokey=True):
-    """The images back to back (in a buffer of pad_to bytes): by i % 3 fresh,
-    carried, carried; of every 500 (at least 5) carried images one with a
-    flipped data bit, and two images with nkey = 0."""
-    offs = np.cumsum([0] + [len(im) for im in items[:-1]]).astype(np.uint64)
-    raw = b"".join(bytes(im) for im in items)
-    buf = np.zeros(pad_to or len(raw), np.uint8)
-    buf[:len(raw)] = np.frombuffer(raw, np.uint8)
-    n = len(items)
-    carried = np.array([i for i in range(n) if i % 3])
-    crcs = np.array([oracle.item_crc(buf, o) for o in offs[carried]], np.uint32)
-    assert (crcs != 0).all()
-    layout.store_crcs(buf, offs[carried], crcs)
-    for i in rng.choice(carried, max(5, n // 500), replace=False).tolist():
-        o = int(offs[i])
-        buf[o + 48 + int(rng.integers(0, layout.ntotal_of(buf, o) - 48))] ^= 1 << int(rng.integers(0, 8))
-    for i in (7, n - 2) if nokey else ():
-        buf[int(offs[i]) + layout.NKEY_OFF] = 0
-    buf.flags.writeable = False
-    return buf, offs
-
-
-@functools.lru_cache(maxsize=None)
-def _items_case(name):
-    rng = np.random.default_rng(len(name) * 1000 + sum(name.encode()))
-    if name.startswith("64"):  # 64 images in exactly 8 MiB (small) or 128 B more (planned)
-        items = [layout.make_item(b"r%05d" % i,
-                                  rng.integers(0, 256, int(rng.integers(0, 9000)), dtype=np.uint8).tobytes(), cas=i + 1)
-                 for i in range(64)]
-        buf, offs = _mixed(items, rng, pad_to=8 * MiB + (128 if name == "64+128" else 0))
-    else:  # 4095 (planned) or 4096 (K5 with a fallback list) images of 4165 B, every 400th of another size
-        n = int(name)
-        vals = [4096 if i % 400 else int(rng.integers(100, 9000)) for i in range(n)]
-        items = [layout.make_item(b"key%07d" % i, rng.integers(0, 256, v, dtype=np.uint8).tobytes(), cas=i + 1)
-                 for i, v in enumerate(vals)]
-        assert len(items[1]) == 4165
-        buf, offs = _mixed(items, rng)
-        assert buf.size > 8 * MiB
-    return buf, offs
-
-
-@functools.lru_cache(maxsize=None)
-def _items_want(name, mode):
-    buf, offs = _items_case(name)
-    if mode == "verify":
-        ok = model.expected_verify(buf, offs, 0)
-        return buf, ok, int((ok == 0).sum())
-    return model.expected_stamp(buf, offs, 0, keep=mode == "keep")
-
-
 @pytest.mark.parametrize("where", ["device", "host"])
 @pytest.mark.parametrize("mode", ["verify", "stamp", "keep"])
 @pytest.mark.parametrize("name", ["64", "64+128", "4095", "4096"])
@@ -154,35 +94,6 @@ def test_item_routes(torch, name, mode, where):
 
 
 # -- pages ---------------------------------------------------------------------
-
-WBUF = 4 * MiB
-
-
-@functools.lru_cache(maxsize=None)
-def _pages_case(nwbufs):
-    """nwbufs 4 MiB wbufs of 4165-B images (1007 each: one wbuf is a small
-    batch, five are past 4096 items) with zero tails, mixed as _mixed makes
-    them but for the nkey = 0 images (they would end their wbuf's walk)."""
-    rng = np.random.default_rng(nwbufs)
-    per = WBUF // 4165
-    buf = np.zeros(nwbufs * WBUF, np.uint8)
-    for w in range(nwbufs):
-        items = [layout.make_item(b"key%07d" % (w * per + i), rng.integers(0, 256, 4096, dtype=np.uint8).tobytes(),
-                                  cas=i + 1) for i in range(per)]
-        part, _ = _mixed(items, rng, nokey=False)
-        buf[w * WBUF:w * WBUF + part.size] = part
-    walked = model.host_walk(buf, WBUF)
-    assert walked.size == nwbufs * per and (nwbufs == 1) == (walked.size <= 4096)
-    buf.flags.writeable = False
-    return buf, walked
-
-
-@functools.lru_cache(maxsize=None)
-def _pages_want(nwbufs):
-    buf, walked = _pages_case(nwbufs)
-    v_ok = model.expected_verify(buf, walked, WBUF)
-    return v_ok, model.expected_stamp(buf, walked, WBUF, keep=True), model.expected_stamp(buf, walked, WBUF, keep=False)
-
 
 def _pages_call(torch, fn, buf, cap, where, flags=0):
     """One direct call of crc32c_verify_pages / crc32c_stamp_pages with result
