@@ -34,6 +34,12 @@
  *                          mismatch, the stored CRC names it; it is flipped back
  *                          and the image proven again.  crc32c_locate_bit is the
  *                          same search for one span on the host (no GPU).
+ *   crc32c_repair_headers  the one image per damaged header that those calls still
+ *                          lose: a flipped bit of nbytes, nkey or the two it_flags
+ *                          bits that decide ITEM_ntotal moves the image's end, and
+ *                          derails its wbuf's walk.  The 42 headers one such bit
+ *                          away are tried, each over its own span; the one whose
+ *                          CRC matches is the header that was written.
  *   crc32c_verify_items    the read-verify compare of storage.c:159-178 applied
  *                          to every item image of a packed extstore page
  *                          (walk of storage.c:950-960): CRC over
@@ -79,7 +85,8 @@ extern "C" {
                               passes disagreed on some wbuf (an internal invariant;
                               the results are not valid) */
 #define CRC32C_EWORK (-7)  /* crc32c_salvage_pages / _recover_pages: the candidates' spans exceed
-                              the work bound; crc32c_repair_items: the damaged images' spans do */
+                              the work bound; crc32c_repair_items: the damaged images' spans do;
+                              crc32c_repair_headers: the candidate variants' spans do */
 
 /* flags */
 #define CRC32C_DEVICE 0x1u    /* every pointer in the batch is device memory of the
@@ -421,6 +428,88 @@ int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes,
  * length-bit and CRLF conditions are the caller's.  4 + len table steps. */
 uint64_t crc32c_locate_bit(uint32_t crc_computed, uint32_t crc_stored, uint64_t len);
 
+/* Undo a flipped length bit in an item header.  crc32c_repair_items leaves the
+ * 42 header bits that decide ITEM_ntotal alone: with one of them inverted the
+ * image's span is no longer the one its CRC was made over.  That image is also
+ * the one whose header derailed its wbuf's walk.  This call tries the 42
+ * headers one such bit away, each with its own span and CRC.
+ *
+ * The rule, per listed offset o = item_offsets[i].  Sanity is
+ * crc32c_verify_items' (region_bytes and CRC32C_CFLAGS64 apply); e is the
+ * little-endian dword at o + 28.  The 42 length bits, by image bit index k (bit
+ * k % 8, LSB = 0, of image byte k / 8): 256..287 (nbytes), 328..335 (nkey), 305
+ * (it_flags bit 1, ITEM_CAS), 312 (it_flags bit 8, ITEM_CFLAGS).
+ *   fewer than 48 bytes left, or o >= base_bytes
+ *                      ok = 0, bit = CRC32C_NO_BIT, lens = 0; nothing is read.
+ *   as it stands       the header is sane and crc32c(0, base + o + 32, nt - 32) ==
+ *                      e: ok = 1, bit = CRC32C_NO_BIT, lens = nt (no CRLF is
+ *                      demanded: crc32c_verify_items' verdict).
+ *   otherwise          variant k is the header with bit k inverted, nt' its
+ *     ITEM_ntotal.  It is a candidate when that header is sane, nbytes' >= 2 and
+ *     the bytes at o + nt' - 2 and o + nt' - 1 are "\r\n" (crc32c_salvage_pages'
+ *     candidate rule; bit k lies inside the span's first ten bytes, so the two
+ *     end bytes are as the buffer has them).  A candidate hits when crc32c(0,
+ *     the span [o + 32, o + nt') with bit k inverted) == e.
+ *     exactly one hit  ok = CRC32C_ITEM_REPAIRED, bit = k, lens = nt'; without
+ *                      CRC32C_LOCATE_ONLY that one bit of the buffer is inverted,
+ *                      so the image then passes crc32c_verify_items.
+ *     none, or several ok = 0, bit = CRC32C_NO_BIT, lens = 0, nothing written: an
+ *                      ambiguous header is not guessed at.
+ * *nrepaired counts ok == CRC32C_ITEM_REPAIRED and *nbad counts ok == 0; both are
+ * always filled.  ok, bit and lens hold n entries.
+ *
+ * The evidence.  Not a syndrome search over 8 nt positions: 42 comparisons of
+ * full 32-bit CRCs, each also gated by the CRLF.  A false repair costs about
+ * 42 * 2^-32 per header at any image length (crc32c_repair_items: 2^-17 for a
+ * 4 KiB image).  So repair headers first, then crc32c_repair_items on what is
+ * still 0, then walk the repaired wbufs again: with its header right, a wbuf's
+ * walk finds everything behind it without a salvage.
+ *
+ * Which offsets to list is the caller's choice.  From crc32c_recover_pages'
+ * output: every kind == 0 entry, with lens 0 or not; and each piece's walk end
+ * when it is not itself an entry (a flip of nkey to 0 ends the walk without
+ * listing the header) -- the end of the piece's last walked entry when that
+ * entry is good, or the piece's start when the piece has no entry -- when at
+ * least 48 bytes remain there (INTEGRATION.md section 4f has the loop).  A
+ * salvaged look-alike inside a repaired image's bytes is the caller's to drop.
+ *
+ * The work bound.  work = the spans of every candidate variant.  work >
+ * CRC32C_HEADER_WORK_MAX * base_bytes: CRC32C_EWORK, nothing is written into the
+ * buffer, the three arrays are unspecified and both counts are 0.  The true
+ * variants of distinct images are disjoint, at most base_bytes together; every
+ * other variant needs a CRLF at one fixed place.  8 leaves room: a cap, not a
+ * tuned number.  What the cap limits is the call's own multiplication of work,
+ * up to 42 spans per listed header, which crafted values could otherwise steer.
+ * What it does not limit: the as-it-stands span of every listed header that is
+ * sane is read once as well and is not in the sum (a header whose flipped
+ * nbytes bit still leaves it sane claims a long one honestly).  That part is
+ * exactly what crc32c_verify_items reads of the same list and, as there,
+ * unbounded: at most n * min(region_bytes, base_bytes) bytes, so a caller who
+ * lists one sane header many times, or overlapping ones, pays for each entry.
+ * Lists built from a walk name disjoint entries and stay within base_bytes.
+ * An offset listed twice below the bound leaves that image's content
+ * unspecified and touches nothing else.
+ *
+ * With CRC32C_DEVICE base, item_offsets, ok, bit and lens are device memory and
+ * the call runs on `stream`; the two counts are host words, read back, so
+ * CRC32C_ASYNC has no effect.  Without it everything is host memory: the buffer
+ * is staged as crc32c_repair_items stages it and the host inverts the accepted
+ * bits in the caller's buffer.  CRC32C_EINVAL: NULL base, item_offsets, ok, bit,
+ * lens, nrepaired or nbad; 43 n >= 2^32 - 1.  n == 0: CRC32C_OK with zero counts;
+ * no device: CRC32C_ENODEV, nothing written.  Reads and writes are bounded as in
+ * crc32c_repair_items.  After the call crc32c_last_kernel_ms() is the time of
+ * the pass that finds and counts the candidate variants (0 for n == 0); the
+ * pass that writes them out is not in it.  Scratch (grow-only): 8 B per header
+ * (a host call 21 B more and the staged buffer), 24 B per candidate beside the
+ * span kernels' own. */
+#define CRC32C_HEADER_BITS 42
+#define CRC32C_HEADER_WORK_MAX 8
+int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes,
+                          const uint64_t *item_offsets, uint64_t n,
+                          uint8_t *ok, uint64_t *bit, uint32_t *lens,
+                          uint64_t *nrepaired, uint64_t *nbad,
+                          unsigned int flags, void *stream);
+
 /* Stamp the spill CRC of n item images (storage.c:567, gathered per wbuf
  * before it is submitted): exptime (bytes 28..31) of image i receives
  * crc32c(0, image + 32, ITEM_ntotal - 32).  Host or device per flags; with
@@ -575,7 +664,8 @@ const char *crc32c_strerror(int err);
 /* Duration of this thread's last synchronous device batch (milliseconds,
  * hipEvent-measured on its stream); -1 before the first one.  After
  * crc32c_salvage_pages and crc32c_recover_pages: the scan's counting pass over
- * the eligible bytes.  After crc32c_repair_items: the search kernel. */
+ * the eligible bytes.  After crc32c_repair_items: the search kernel.  After
+ * crc32c_repair_headers: the variants' counting pass. */
 float crc32c_last_kernel_ms(void);
 
 #ifdef __cplusplus

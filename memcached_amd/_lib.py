@@ -37,6 +37,8 @@ CRC32C_ITEM_REPAIRED = 5  # ok[] of crc32c_repair_items: one bit located (and fl
 CRC32C_NO_BIT = 2**64 - 1  # bit[] of crc32c_repair_items / crc32c_locate_bit: no position
 CRC32C_REPAIR_SPAN_DEFAULT = 0x200000  # crc32c_repair_items' max_span when 0 is passed
 CRC32C_REPAIR_SPAN_MAX = 0x0FFFFFC0  # the longest span whose located position is unique
+CRC32C_HEADER_BITS = 42  # crc32c_repair_headers: the header bits that decide ITEM_ntotal, one variant each
+CRC32C_HEADER_WORK_MAX = 8  # its work bound: the candidate variants' spans per byte of the buffer
 CRC32C_MAX_SPAN = 0x7FFF0000  # longest span (include/crc32c_batch.h)
 CRC32C_SALVAGE_WORK_MAX = 64  # crc32c_salvage_pages' work bound: candidates' spans per scanned byte
 
@@ -49,6 +51,7 @@ EXPORTED = (
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
     "crc32c_set_k1_tail_min", "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit",
+    "crc32c_repair_headers",
 )
 
 
@@ -99,6 +102,7 @@ PROTOTYPES = {
                                     _PTR]),
     "crc32c_repair_items": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _U32, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
     "crc32c_locate_bit": (_U64, [_U32, _U32, _U64]),
+    "crc32c_repair_headers": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _PTR, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
     "crc32c_batch_chains": (_INT, [_SPANS, _PTR, _U64, _PTR, _UINT, _PTR]),
     "crc32c_host_alloc": (_PTR, [_SIZE]),
     "crc32c_host_free": (None, [_PTR]),
@@ -115,7 +119,7 @@ PROTOTYPES = {
 }
 # what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
 NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min",
-         "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit")
+         "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit", "crc32c_repair_headers")
 
 
 def _load():

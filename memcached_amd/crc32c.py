@@ -15,6 +15,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``recover_pages`` verify_pages + salvage_pages in one call, one merged list
 * ``repair_items`` single-bit damage of item images located by the stored CRC and flipped back
   (``locate_bit``: the same search for one span on the host)
+* ``repair_headers`` a flipped length bit of an item header found among the 42 headers one bit away
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
 
@@ -33,7 +34,7 @@ import numpy as np
 from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
-# (recover_pages, repair_items and locate_bit are public as well; tests/test_python_face.py pins this list as it
+# (recover_pages, repair_items, locate_bit and repair_headers are public as well; tests/test_python_face.py pins this list as it
 # stood before them)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
@@ -486,6 +487,39 @@ def repair_items(buf, item_offsets, region_bytes=0, max_span=0, locate_only=Fals
                                   ctypes.byref(nrepaired), ctypes.byref(nbad), flags, side.stream),
           "crc32c_repair_items")
     return ok, bit, {"nrepaired": int(nrepaired.value), "nbad": int(nbad.value)}
+
+
+def repair_headers(buf, item_offsets, region_bytes=0, locate_only=False, stream=None, cflags64=False):
+    """Undo a flipped length bit in item headers (crc32c_repair_headers): for
+    every listed header that does not verify as it stands, the 42 headers with
+    one bit of nbytes, nkey or the two it_flags bits that decide ITEM_ntotal
+    inverted are tried, each over its own span; when exactly one of them is
+    sane, ends in CRLF and has the stored CRC, that bit is inverted again in
+    ``buf``.
+
+    Returns (ok, bit, lens, {"nrepaired", "nbad"}) for numpy and torch buffers:
+    ok[i] is 1 for an image that verifies as it stands, CRC32C_ITEM_REPAIRED (5)
+    for a repaired header with bit[i] the image's bit index (bit k % 8 of image
+    byte k // 8), else 0 with bit[i] = CRC32C_NO_BIT; lens[i] is the image's
+    ITEM_ntotal (0 with ok 0).  The list is the caller's: from recover_pages,
+    every kind 0 entry and each piece's walk end that is not itself an entry
+    (include/crc32c_batch.h).  ``locate_only``: the same verdicts, ``buf`` is
+    left as it is; a host buffer that is not a writable contiguous uint8 numpy
+    array is accepted only so.  ``region_bytes`` and ``cflags64`` as for
+    verify_items.  Raises Crc32cError(CRC32C_EWORK) when the candidate
+    variants' spans add up to more than CRC32C_HEADER_WORK_MAX times the buffer."""
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf, inplace=None if locate_only else
+                              "repair_headers needs {} (repaired in place) unless locate_only is set")
+    offs = side.desc(item_offsets, "item_offsets", _U64)
+    n = _count(offs)
+    ok, bit, lens = side.empty(n, _U8), side.empty(n, _U64), side.empty(n, _U32)
+    nrepaired, nbad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    flags = side.flag | _flags(cflags64) | (_lib.CRC32C_LOCATE_ONLY if locate_only else 0)
+    check(lib.crc32c_repair_headers(_ptr(buf), nbytes, region_bytes, _ptr(offs), n, _ptr(ok), _ptr(bit), _ptr(lens),
+                                    ctypes.byref(nrepaired), ctypes.byref(nbad), flags, side.stream),
+          "crc32c_repair_headers")
+    return ok, bit, lens, {"nrepaired": int(nrepaired.value), "nbad": int(nbad.value)}
 
 
 def locate_bit(crc_computed: int, crc_stored: int, length: int) -> int:

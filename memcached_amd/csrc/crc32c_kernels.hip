@@ -42,3 +42,4 @@
 #include "k_salvage.h" // crc32c_salvage_pages: k_salvage_regions, k_salvage_scan, k_salvage_pick
 #include "k_recover.h" // crc32c_recover_pages: k_recover_regions, k_recover_merge
 #include "k_repair.h"  // crc32c_repair_items: k_repair_count, k_repair_emit, k_repair_search, k_repair_apply
+#include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply

@@ -61,6 +61,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_salvage.h"
 #include "shim_recover.h"
 #include "shim_repair.h"
+#include "shim_header.h"
 
 // Batch C ABI
 extern "C" {
@@ -351,6 +352,13 @@ int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, 
                         unsigned flags, void *stream) {
     return repair_items(base, base_bytes, region_bytes, item_offsets, n, max_span, ok, bit, nrepaired, nbad, flags,
                         stream);
+}
+
+int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets,
+                          uint64_t n, uint8_t *ok, uint64_t *bit, uint32_t *lens, uint64_t *nrepaired, uint64_t *nbad,
+                          unsigned flags, void *stream) {
+    return repair_headers(base, base_bytes, region_bytes, item_offsets, n, ok, bit, lens, nrepaired, nbad, flags,
+                          stream);
 }
 
 int crc32c_shard_cuts(const uint32_t *lens, uint32_t len, uint64_t n, int parts, uint64_t *cuts) {

@@ -146,6 +146,17 @@ struct Device {
     DevBuf<uint8_t> rp_ok;
     DevBuf<uint64_t> rp_bit;
     PinBuf<uint64_t> rp_hbit;
+    // crc32c_repair_headers: per header its candidates' count and scan; per
+    // candidate its span (offset, length), record and CRC; the counters and
+    // their pinned twin; a host call's verdicts, positions and lengths
+    DevBuf<uint32_t> hd_cnt, hd_pre, hd_len, hd_crc, hd_lens;
+    DevBuf<uint64_t> hd_off, hd_bit;
+    DevBuf<mcrc_dev::HeaderRec> hd_recs;
+    DevBuf<unsigned long long> hd_ctr;
+    PinBuf<unsigned long long> hd_host;
+    DevBuf<uint8_t> hd_ok;
+    PinBuf<uint64_t> hd_hbit;
+    PinBuf<uint32_t> hd_hlens;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;
