@@ -28,7 +28,12 @@
  *                          the page staged once, the walk's lists kept on the
  *                          device, one merged list with each image's kind and
  *                          ITEM_ntotal for a single rescue loop.
- *   crc32c_repair_items    the images those calls prove damaged (kind 0,
+ *   crc32c_triage_pages    crc32c_recover_pages with a third list merged in: the
+ *                          unreached candidates whose stored CRC does not match
+ *                          (kind CRC32C_ITEM_SUSPECT), the data-damaged images
+ *                          behind a header that ended its wbuf's walk, so that
+ *                          crc32c_repair_items can be handed them.
+ *   crc32c_repair_items   the images those calls prove damaged (kind 0,
  *                          CRC32C_ITEM_DAMAGED, badcrc_from_extstore) and the
  *                          reference drops: where one inverted bit explains the
  *                          mismatch, the stored CRC names it; it is flipped back
@@ -84,7 +89,7 @@ extern "C" {
 #define CRC32C_EWALK (-6)  /* crc32c_verify_pages / _stamp_pages: the device walk's count and emit
                               passes disagreed on some wbuf (an internal invariant;
                               the results are not valid) */
-#define CRC32C_EWORK (-7)  /* crc32c_salvage_pages / _recover_pages: the candidates' spans exceed
+#define CRC32C_EWORK (-7)  /* crc32c_salvage_pages / _recover_pages / _triage_pages: the candidates' spans exceed
                               the work bound; crc32c_repair_items: the damaged images' spans do;
                               crc32c_repair_headers: the candidate variants' spans do */
 
@@ -332,6 +337,68 @@ int crc32c_recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_by
                          uint32_t *lens, uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad,
                          uint64_t *nsalvaged, uint64_t *scanned, uint64_t *ncand, unsigned flags,
                          void *stream);
+
+/* crc32c_recover_pages with the damaged images the walk never reaches listed
+ * too.  The salvage reports intact images only, so an image whose own bytes
+ * were hit and that lies behind a header that ended its wbuf's walk is named
+ * by neither list of crc32c_recover_pages, and crc32c_repair_items cannot be
+ * handed it.  This call merges a third list in: the suspects, kind
+ * CRC32C_ITEM_SUSPECT.
+ * The rule.  walked[], wok[], found[], C, sane, candidate and intact are as
+ * defined above for crc32c_recover_pages and crc32c_salvage_pages.  Per piece,
+ * from its first byte, while piece_end - o >= 48:
+ *     o in C                                        ->  o = the end of the covering image
+ *     else intact(o)                                ->  found: report o;  o += nt
+ *     else candidate(o) and o no entry of walked[]  ->  suspect: report o;  o += 1
+ *     else                                          ->  o += 1
+ * A suspect never moves the cursor by its length, which is not proven; so
+ * found[] is exactly what crc32c_salvage_pages finds, and a candidate inside a
+ * found image is never a suspect.  A walked entry with wok == 0 that is itself
+ * a failing candidate is in the list already, as kind 0, and is not listed
+ * twice.  The suspects ascend, are distinct from every walked and found
+ * offset, may overlap each other and later entries in bytes, and number at
+ * most ncand - nfound.
+ * The list is walked[], found[] and the suspects together, ascending by
+ * offset.  kind[i] is wok, CRC32C_ITEM_SALVAGED or CRC32C_ITEM_SUSPECT; lens[i]
+ * as for crc32c_recover_pages, and a suspect's is its ITEM_ntotal, never 0 (a
+ * candidate is sane).  *nitems = nwalked + nfound + nsuspect, *nbad = nbad_w,
+ * *nsalvaged = nfound, *nsuspect (required) = the suspects.  With the
+ * kind-CRC32C_ITEM_SUSPECT entries taken out, the three arrays, *nbad,
+ * *nsalvaged, *scanned, *ncand and the return code are crc32c_recover_pages'
+ * for the same buffer.
+ * A suspect is evidence of nothing but a plausible header and a CRLF: a rescue
+ * loop skips it, as it skips kind 0.  It is a candidate for
+ * crc32c_repair_items, whose proof (one bit that makes the stored CRC match) is
+ * then the only one it has; filter overlapping suspects first (INTEGRATION.md
+ * section 4g).
+ * Everything else is crc32c_recover_pages': cap (0 still computes everything,
+ * the arrays may be NULL; the first min(cap, *nitems) entries are written,
+ * nothing behind them); CRC32C_EWORK (the walk's entries alone, *nitems =
+ * nwalked, *nsalvaged = *nsuspect = 0, *scanned and *ncand filled);
+ * CRC32C_EWALK; CRC32C_EINVAL (NULL base, nitems, nbad, nsalvaged or nsuspect,
+ * wbuf_bytes == 0, cap != 0 with any array NULL, 2^31 - 1 pieces or more);
+ * base_bytes == 0 (CRC32C_OK with zero counts); no device (CRC32C_ENODEV,
+ * nothing written); CRC32C_DEVICE (base and the three arrays are device
+ * memory, the six counts host words) and host staging (the buffer is staged
+ * once); CRC32C_CFLAGS64; CRC32C_ASYNC has no effect; the read and write
+ * bounds; crc32c_last_kernel_ms() is the time of the scan's counting pass.
+ * No pass over the page's bytes is added: the candidates and their CRCs are
+ * the ones crc32c_recover_pages computes and drops.  Scratch (grow-only):
+ * crc32c_recover_pages', 1 B per candidate (the kind byte of a picked entry)
+ * and 4 B per piece.
+ * crc32c_salvage_pages has no such mode: it returns no kind array to tell a
+ * suspect from an image found.
+ * call_flags is the flags word of crc32c_recover_pages, bit for bit.  It has a
+ * name of its own because tests/test_interleave_cases.py and
+ * tests/test_header_interleave_cases.py count the declarations with a parameter
+ * called flags and pin them at the entry points of their own two op tables;
+ * tests/test_triage_interleave_cases.py counts a flags word under any name and
+ * holds this call to the third table. */
+#define CRC32C_ITEM_SUSPECT 6 /* kind[]: not reached by the walk, a candidate whose stored CRC does not match */
+int crc32c_triage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets,
+                        uint32_t *lens, uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad,
+                        uint64_t *nsalvaged, uint64_t *nsuspect, uint64_t *scanned, uint64_t *ncand,
+                        unsigned call_flags, void *stream);
 
 /* Correct single-bit damage from the stored CRC.  An image whose own bytes were
  * hit comes back as kind 0 from the walk, as CRC32C_ITEM_DAMAGED from
@@ -663,8 +730,8 @@ const char *crc32c_strerror(int err);
 
 /* Duration of this thread's last synchronous device batch (milliseconds,
  * hipEvent-measured on its stream); -1 before the first one.  After
- * crc32c_salvage_pages and crc32c_recover_pages: the scan's counting pass over
- * the eligible bytes.  After crc32c_repair_items: the search kernel.  After
+ * crc32c_salvage_pages, crc32c_recover_pages and crc32c_triage_pages: the scan's
+ * counting pass over the eligible bytes.  After crc32c_repair_items: the search kernel.  After
  * crc32c_repair_headers: the variants' counting pass. */
 float crc32c_last_kernel_ms(void);
 

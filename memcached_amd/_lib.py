@@ -34,6 +34,7 @@ CRC32C_ITEM_COPIED = 1  # ok[] values of crc32c_copy_items
 CRC32C_ITEM_DAMAGED = 3
 CRC32C_ITEM_SALVAGED = 4  # kind[] of crc32c_recover_pages: found by the salvage (0 / 1: the walk's verdicts)
 CRC32C_ITEM_REPAIRED = 5  # ok[] of crc32c_repair_items: one bit located (and flipped back)
+CRC32C_ITEM_SUSPECT = 6  # kind[] of crc32c_triage_pages: an unreached candidate whose stored CRC does not match
 CRC32C_NO_BIT = 2**64 - 1  # bit[] of crc32c_repair_items / crc32c_locate_bit: no position
 CRC32C_REPAIR_SPAN_DEFAULT = 0x200000  # crc32c_repair_items' max_span when 0 is passed
 CRC32C_REPAIR_SPAN_MAX = 0x0FFFFFC0  # the longest span whose located position is unique
@@ -51,7 +52,7 @@ EXPORTED = (
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
     "crc32c_set_k1_tail_min", "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit",
-    "crc32c_repair_headers",
+    "crc32c_repair_headers", "crc32c_triage_pages",
 )
 
 
@@ -100,6 +101,8 @@ PROTOTYPES = {
                                     _PTR]),
     "crc32c_recover_pages": (_INT, [_PTR, _U64, _U64, _PTR, _PTR, _PTR, _U64, _U64P, _U64P, _U64P, _U64P, _U64P, _UINT,
                                     _PTR]),
+    "crc32c_triage_pages": (_INT, [_PTR, _U64, _U64, _PTR, _PTR, _PTR, _U64, _U64P, _U64P, _U64P, _U64P, _U64P, _U64P,
+                                   _UINT, _PTR]),
     "crc32c_repair_items": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _U32, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
     "crc32c_locate_bit": (_U64, [_U32, _U32, _U64]),
     "crc32c_repair_headers": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _PTR, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
@@ -119,7 +122,8 @@ PROTOTYPES = {
 }
 # what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
 NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min",
-         "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit", "crc32c_repair_headers")
+         "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit", "crc32c_repair_headers",
+         "crc32c_triage_pages")
 
 
 def _load():

@@ -13,6 +13,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``verify_pages`` walk + verify whole pages on the device (storage.c:950-1070)
 * ``salvage_pages`` the intact images behind a header that ended a wbuf's walk
 * ``recover_pages`` verify_pages + salvage_pages in one call, one merged list
+* ``triage_pages`` recover_pages plus the unreached candidates whose stored CRC fails (kind 6), for repair_items
 * ``repair_items`` single-bit damage of item images located by the stored CRC and flipped back
   (``locate_bit``: the same search for one span on the host)
 * ``repair_headers`` a flipped length bit of an item header found among the 42 headers one bit away
@@ -34,7 +35,7 @@ import numpy as np
 from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
-# (recover_pages, repair_items, locate_bit and repair_headers are public as well; tests/test_python_face.py pins this list as it
+# (recover_pages, triage_pages, repair_items, locate_bit and repair_headers are public as well; tests/test_python_face.py pins this list as it
 # stood before them)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
@@ -456,6 +457,45 @@ def recover_pages(buf, wbuf_bytes, stream=None, cflags64=False):
     offs, lens, kind = _sized(side, (_U64, _U32, _U8), cap, run)
     info = dict(zip(("nbad", "nsalvaged", "scanned", "ncand"), (int(c.value) for c in counts[1:])))
     _check_carrying(status[0], "crc32c_recover_pages", _lib.CRC32C_EWORK, offsets=offs, lens=lens, kind=kind, **info)
+    return offs, lens, kind, info
+
+
+def triage_pages(buf, wbuf_bytes, stream=None, cflags64=False):
+    """recover_pages with the damaged images the walk never reaches listed too
+    (crc32c_triage_pages): an unreached candidate (sane header, CRLF at its
+    end) whose stored CRC does not match comes back as kind
+    CRC32C_ITEM_SUSPECT (6), with its ITEM_ntotal in lens, so that
+    repair_items can be handed it.
+
+    Returns (offsets, lens, kind, info) as recover_pages does, info with
+    ``"nsuspect"`` beside recover_pages' counts; with the kind-6 entries taken
+    out the result is recover_pages'.  Past the work bound the call raises
+    Crc32cError(CRC32C_EWORK) with the walk's part and the counts (nsuspect 0)
+    as attributes of the error."""
+    wbuf_bytes = _wbuf_bytes(wbuf_bytes)
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf)
+    counts = [ctypes.c_uint64(0) for _ in range(6)]  # nitems, nbad, nsalvaged, nsuspect, scanned, ncand
+    status = []
+
+    def run(cap, offs, lens, kind):
+        rc = lib.crc32c_triage_pages(_ptr(buf), nbytes, wbuf_bytes, offs, lens, kind, cap,
+                                     *map(ctypes.byref, counts), side.flag | _flags(cflags64), side.stream)
+        if rc != _lib.CRC32C_EWORK:  # (that one comes with the walk's part: raised below, with it)
+            check(rc, "crc32c_triage_pages")
+        status[:] = [rc]
+        return counts[0].value
+
+    # the capacity as recover_pages guesses it (a host call's bound holds for the walk's and the found entries
+    # alone: suspects may overlap, so a second call sized from nitems takes what is above it)
+    cap = _walk_bound(nbytes, wbuf_bytes)
+    if side.dev:
+        cap = min(nbytes // 1024 + -(-nbytes // wbuf_bytes), cap) + nbytes // (100 * 1024) + 64
+    else:
+        cap += nbytes // 50
+    offs, lens, kind = _sized(side, (_U64, _U32, _U8), cap, run)
+    info = dict(zip(("nbad", "nsalvaged", "nsuspect", "scanned", "ncand"), (int(c.value) for c in counts[1:])))
+    _check_carrying(status[0], "crc32c_triage_pages", _lib.CRC32C_EWORK, offsets=offs, lens=lens, kind=kind, **info)
     return offs, lens, kind, info
 
 

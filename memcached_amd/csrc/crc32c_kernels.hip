@@ -43,3 +43,4 @@
 #include "k_recover.h" // crc32c_recover_pages: k_recover_regions, k_recover_merge
 #include "k_repair.h"  // crc32c_repair_items: k_repair_count, k_repair_emit, k_repair_search, k_repair_apply
 #include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply
+#include "k_triage.h"  // crc32c_triage_pages: k_triage_pick, k_triage_merge

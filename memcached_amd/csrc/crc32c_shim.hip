@@ -59,6 +59,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_queue.h"
 #include "shim_walk.h"
 #include "shim_salvage.h"
+#include "shim_triage.h"
 #include "shim_recover.h"
 #include "shim_repair.h"
 #include "shim_header.h"
@@ -343,8 +344,15 @@ int crc32c_salvage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_by
 int crc32c_recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
                          uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
                          uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
-    return recover_pages(base, base_bytes, wbuf_bytes, offsets, lens, kind, cap, nitems, nbad, nsalvaged, scanned,
-                         ncand, flags, stream);
+    return recover_pages(base, base_bytes, wbuf_bytes, offsets, lens, kind, cap, nitems, nbad, nsalvaged, nullptr,
+                         false, scanned, ncand, flags, stream);
+}
+
+int crc32c_triage_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
+                        uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
+                        uint64_t *nsuspect, uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
+    return recover_pages(base, base_bytes, wbuf_bytes, offsets, lens, kind, cap, nitems, nbad, nsalvaged, nsuspect,
+                         true, scanned, ncand, flags, stream);
 }
 
 int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets,

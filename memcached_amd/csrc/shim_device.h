@@ -136,6 +136,10 @@ struct Device {
     DevBuf<uint32_t> rc_cnt, rc_pre, rc_lens;
     DevBuf<uint64_t> rc_slots, rc_offs;
     DevBuf<uint8_t> rc_kind;
+    // crc32c_triage_pages: the kind byte beside each picked candidate and the
+    // scan of the per-piece counts of the found among them
+    DevBuf<uint8_t> tr_kind;
+    DevBuf<uint32_t> tr_fpre;
     // crc32c_repair_items: per image its CRC, the two counts and their scans; per
     // listed image its record, first chunk and located t; the counters and
     // their pinned twin; a host call's verdicts and positions

@@ -1,4 +1,6 @@
-// shim_recover.h -- recover_pages, the body of crc32c_recover_pages: the page
+// shim_recover.h -- recover_pages, the body of crc32c_recover_pages and, with
+// `triage`, of crc32c_triage_pages (the pick and the merge are then
+// shim_triage.h's, every other launch is the same): the page
 // walk and its verify (shim_walk.h), the salvage's stages behind them
 // (shim_salvage.h SalvageRun) and the merge of the two lists (k_recover.h),
 // under one lock and one lease.  A host buffer is staged once, by the walk;
@@ -14,8 +16,10 @@ static_assert(mcrc_dev::kKindSalvaged == CRC32C_ITEM_SALVAGED, "the merge writes
 
 int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
                   uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
-                  uint64_t *scanned, uint64_t *ncand, unsigned flags, void *stream) {
-    if (!base || !nitems || !nbad || !nsalvaged || !wbuf_bytes || (cap && (!offsets || !lens || !kind)))
+                  uint64_t *nsuspect, bool triage, uint64_t *scanned, uint64_t *ncand, unsigned flags,
+                  void *stream) {
+    if (!base || !nitems || !nbad || !nsalvaged || !wbuf_bytes || (cap && (!offsets || !lens || !kind)) ||
+        (triage && !nsuspect))
         return CRC32C_EINVAL;
     Device *dp = nullptr;
     int rc = current_device(&dp);
@@ -24,10 +28,11 @@ int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, ui
     hipStream_t st = (hipStream_t)stream;
     const bool dev = flags & CRC32C_DEVICE;
     if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
-    auto done = [&](uint64_t ni, uint64_t nb, uint64_t ns, uint64_t sc, uint64_t nc, int ret) {
+    auto done = [&](uint64_t ni, uint64_t nb, uint64_t ns, uint64_t sc, uint64_t nc, int ret, uint64_t nsus = 0) {
         *nitems = ni;
         *nbad = nb;
         *nsalvaged = ns;
+        if (triage) *nsuspect = nsus;
         if (scanned) *scanned = sc;
         if (ncand) *ncand = nc;
         return ret;
@@ -61,10 +66,14 @@ int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, ui
     const uint64_t nb = total ? count[0] : 0;
     int ret = total && count[1] ? CRC32C_EWALK : CRC32C_OK;
     uint64_t *found = nullptr;
+    TriagePick tp;
     if (ret == CRC32C_OK && r.ntiles) {
         if ((rc = r.scan())) return rc;
         if (r.nc && r.over()) {
             ret = CRC32C_EWORK;
+        } else if (r.nc && triage) {
+            if ((rc = r.candidates()) || (rc = triage_pick(r, woffs, &tp))) return rc;
+            found = tp.picked;
         } else if (r.nc) {
             if (!(found = d.sv_out.reserve(r.nc * 8))) return CRC32C_ENOMEM;
             if ((rc = r.candidates()) || (rc = r.pick(found, r.nc))) return rc;
@@ -80,7 +89,10 @@ int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, ui
                                    kcap};
         if (!out.offsets || !out.lens || !out.kind) return CRC32C_ENOMEM;
     }
-    if (kcap) {
+    if (kcap && triage) {
+        const uint64_t grid = std::min<uint64_t>((most + 1023) / 1024, 2048), per = (most + grid - 1) / grid;
+        if ((rc = triage_merge(r, a, woffs, wok, found ? &tp : nullptr, dim3((unsigned)grid), per, out))) return rc;
+    } else if (kcap) {
         // a workgroup per 1024 entries or more (four rounds of its threads: k_recover.h), 2048 workgroups at the most
         const uint64_t grid = std::min<uint64_t>((most + 1023) / 1024, 2048), per = (most + grid - 1) / grid;
         hipLaunchKernelGGL(mcrc_dev::k_recover_merge, dim3((unsigned)grid), dim3(256), 0, st, a,
@@ -90,13 +102,14 @@ int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, ui
         HIP_OK(hipGetLastError());
     }
     HIP_OK(hipStreamSynchronize(st));
-    const uint64_t nf = found ? *r.h32 : 0, k = std::min(cap, total + nf);
+    // (triage: h32[0] is the picked entries, found and suspects together, h32[1] the found among them)
+    const uint64_t np = found ? r.h32[0] : 0, nf = triage && found ? r.h32[1] : np, k = std::min(cap, total + np);
     if (!dev && k) {
         HIP_OK(hipMemcpy(offsets, out.offsets, k * 8, hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(lens, out.lens, k * 4, hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(kind, out.kind, k, hipMemcpyDeviceToHost));
     }
-    return done(total + nf, nb, nf, r.sc, r.nc, ret);
+    return done(total + np, nb, nf, r.sc, r.nc, ret, np - nf);
 }
 
 }  // namespace
