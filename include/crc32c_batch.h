@@ -577,6 +577,115 @@ int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes
                           uint64_t *nrepaired, uint64_t *nbad,
                           unsigned int flags, void *stream);
 
+/* A page's whole repair flow in one call: crc32c_triage_pages, rounds of
+ * crc32c_repair_headers over the list that INTEGRATION.md section 4f builds
+ * from it, crc32c_repair_items over the list of section 4g, and the triage
+ * again after every round that repaired something, until nothing more can be
+ * repaired.  The page crosses the link once, the lists between the stages
+ * stay on the device, and the caller gets the final triage list and a log of
+ * every bit that was inverted.
+ *
+ * The rule is a composition of the three calls and nothing else.  With
+ * region_bytes = wbuf_bytes, the CRC32C_CFLAGS64 bit of opts->mode and the
+ * repairs writing in place:
+ *
+ *   header_list(T): per piece every kind-0 entry, then the piece's walk end
+ *     (the end of its last walked entry, kinds 4 and 6 skipped; the piece's
+ *     start when it has none) when that entry is not kind 0 and at least 48
+ *     bytes of the piece remain there;
+ *   item_list(T): every entry with kind == 0 && lens != 0, and every suspect
+ *     that ends at or before the next kind-1 or kind-4 entry and starts at or
+ *     behind the end of the last suspect kept, in one ascending list;
+ *
+ *   T = triage
+ *   loop: T failed (CRC32C_EWORK, CRC32C_EWALK): return its status, T is what
+ *           crc32c_triage_pages returns then;
+ *         h = repair_headers(header_list(T)); h failed: return its status (it
+ *           wrote nothing, T still describes the page);
+ *         h repaired something: log its flips, one more round, T = triage,
+ *           stop at max_rounds, else start the loop again (headers before
+ *           items, every time);
+ *         i = repair_items(item_list(T), max_span); i failed: return its status;
+ *         i repaired nothing: complete = 1, stop (T describes the page);
+ *         log its flips, one more round, T = triage, stop at max_rounds.
+ *
+ * Outputs.  offsets / lens / kind take the first min(cap, nitems) entries of
+ * the last T, and nitems, nbad, nsalvaged, nsuspect, scanned and ncand are
+ * its counts, all as crc32c_triage_pages reports them.  The log has one entry
+ * per bit inverted, in the order made (round by round, in a round in list
+ * order): flip_offsets[r] the image's offset, flip_bits[r] the image's bit
+ * index as the repair call reported it (buffer bit 8 * offset + index),
+ * flip_by[r] the stage; its first min(flip_cap, nflips) entries are written.
+ * Nothing is written behind either, cap == 0 or flip_cap == 0 means those
+ * arrays may be NULL, and every count is exact whatever the caps are.  With
+ * CRC32C_DEVICE the six arrays are device memory; the counts are host words.
+ * rounds counts the repair calls that repaired something.
+ *
+ * complete == 1: the flow ended because nothing more could be repaired.  The
+ * result is then a fixpoint: a second call on the result inverts nothing and
+ * returns the same list.  complete == 0 with CRC32C_OK: max_rounds (0:
+ * CRC32C_SCRUB_ROUNDS_DEFAULT) was reached; what was repaired stays repaired
+ * and is logged.
+ *
+ * A host buffer (no CRC32C_DEVICE) is staged once, every stage runs on the
+ * staged copy, and at the end the host inverts the logged bits in the
+ * caller's buffer, whatever flip_cap is.  With CRC32C_LOCATE_ONLY those
+ * inversions are left out: the list and the log describe the page as it
+ * would be and the caller's bytes are untouched.  A device buffer with
+ * CRC32C_LOCATE_ONLY is CRC32C_EINVAL: the rounds need the earlier flips in
+ * place and the library keeps no second copy of a device page.
+ *
+ * Evidence.  Exactly that of the calls composed: a header repair is wrong
+ * with probability 42 * 2^-32 per header, an item repair with (8 nt - 224) /
+ * 2^32 per item (see crc32c_repair_headers and crc32c_repair_items).  A
+ * caller who wants to treat repaired images apart finds them through the log.
+ *
+ * CRC32C_EINVAL: NULL base or out, wbuf_bytes == 0, cap or flip_cap non-zero
+ * with one of its arrays NULL, max_span above CRC32C_REPAIR_SPAN_MAX, 2^31 - 1
+ * pieces or more, a header list longer than crc32c_repair_headers takes.
+ * base_bytes == 0: CRC32C_OK, zero counts, complete = 1.  No device:
+ * CRC32C_ENODEV, and neither `out` nor any array is written, not even partly
+ * (CRC32C_EINVAL, CRC32C_ENOMEM and CRC32C_EHIP write nothing into `out`
+ * either).  CRC32C_ASYNC has no effect.  Reads and writes stay inside the
+ * bounds of the three calls.  crc32c_last_kernel_ms: the last triage's
+ * counting pass.
+ *
+ * Scratch (grow-only) beyond that of the three calls: per entry of the merged
+ * list 13 B (the whole list stays on the device, not its first cap entries);
+ * per piece 8 B of count and scan; per entry of a repair list 8 B of offset
+ * and the repair calls' 9 B (items) or 13 B (headers) of verdicts; a host
+ * call: the staged page and 17 B per flip of a round. */
+#define CRC32C_SCRUB_ROUNDS_DEFAULT 64
+#define CRC32C_SCRUB_BY_HEADER 1 /* flip_by[]: made by the crc32c_repair_headers stage */
+#define CRC32C_SCRUB_BY_ITEM 2   /* flip_by[]: made by the crc32c_repair_items stage */
+
+typedef struct crc32c_scrub_opts { /* NULL: all zero */
+    uint32_t mode;       /* CRC32C_DEVICE | CRC32C_CFLAGS64 | CRC32C_LOCATE_ONLY; other bits ignored */
+    uint32_t max_span;   /* crc32c_repair_items' max_span, same meaning, same CRC32C_EINVAL */
+    uint32_t max_rounds; /* 0: CRC32C_SCRUB_ROUNDS_DEFAULT */
+    void *stream;
+} crc32c_scrub_opts;
+
+typedef struct crc32c_scrub_out {
+    /* in: the caller's arrays (device memory with CRC32C_DEVICE) and their room */
+    uint64_t *offsets;
+    uint32_t *lens;
+    uint8_t *kind;
+    uint64_t cap;
+    uint64_t *flip_offsets;
+    uint64_t *flip_bits;
+    uint8_t *flip_by;
+    uint64_t flip_cap;
+    /* out: always filled, host words */
+    uint64_t nitems, nbad, nsalvaged, nsuspect, scanned, ncand; /* the final list's, as crc32c_triage_pages' */
+    uint64_t nflips, headers_repaired, items_repaired;
+    uint32_t rounds;   /* repair calls that repaired something */
+    uint32_t complete; /* 1: the flow ended because nothing more could be repaired */
+} crc32c_scrub_out;
+
+int crc32c_scrub_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes,
+                       const crc32c_scrub_opts *opts, crc32c_scrub_out *out);
+
 /* Stamp the spill CRC of n item images (storage.c:567, gathered per wbuf
  * before it is submitted): exptime (bytes 28..31) of image i receives
  * crc32c(0, image + 32, ITEM_ntotal - 32).  Host or device per flags; with
@@ -732,7 +841,8 @@ const char *crc32c_strerror(int err);
  * hipEvent-measured on its stream); -1 before the first one.  After
  * crc32c_salvage_pages, crc32c_recover_pages and crc32c_triage_pages: the scan's
  * counting pass over the eligible bytes.  After crc32c_repair_items: the search kernel.  After
- * crc32c_repair_headers: the variants' counting pass. */
+ * crc32c_repair_headers: the variants' counting pass.  After
+ * crc32c_scrub_pages: its last triage's counting pass. */
 float crc32c_last_kernel_ms(void);
 
 #ifdef __cplusplus

@@ -40,6 +40,9 @@ CRC32C_REPAIR_SPAN_DEFAULT = 0x200000  # crc32c_repair_items' max_span when 0 is
 CRC32C_REPAIR_SPAN_MAX = 0x0FFFFFC0  # the longest span whose located position is unique
 CRC32C_HEADER_BITS = 42  # crc32c_repair_headers: the header bits that decide ITEM_ntotal, one variant each
 CRC32C_HEADER_WORK_MAX = 8  # its work bound: the candidate variants' spans per byte of the buffer
+CRC32C_SCRUB_ROUNDS_DEFAULT = 64  # crc32c_scrub_pages' max_rounds when 0 is passed
+CRC32C_SCRUB_BY_HEADER = 1  # its flip_by[]: made by the crc32c_repair_headers stage
+CRC32C_SCRUB_BY_ITEM = 2  # ... by the crc32c_repair_items stage
 CRC32C_MAX_SPAN = 0x7FFF0000  # longest span (include/crc32c_batch.h)
 CRC32C_SALVAGE_WORK_MAX = 64  # crc32c_salvage_pages' work bound: candidates' spans per scanned byte
 
@@ -52,7 +55,7 @@ EXPORTED = (
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
     "crc32c_set_k1_tail_min", "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit",
-    "crc32c_repair_headers", "crc32c_triage_pages",
+    "crc32c_repair_headers", "crc32c_triage_pages", "crc32c_scrub_pages",
 )
 
 
@@ -74,6 +77,41 @@ class Spans(ctypes.Structure):
         ("crc_in", ctypes.c_void_p),
         ("out", ctypes.c_void_p),
         ("n", ctypes.c_uint64),
+    ]
+
+
+class ScrubOpts(ctypes.Structure):
+    """crc32c_scrub_opts"""
+    _fields_ = [
+        ("mode", ctypes.c_uint32),
+        ("max_span", ctypes.c_uint32),
+        ("max_rounds", ctypes.c_uint32),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
+class ScrubOut(ctypes.Structure):
+    """crc32c_scrub_out: the caller's arrays and their room, then the counts the call fills"""
+    _fields_ = [
+        ("offsets", ctypes.c_void_p),
+        ("lens", ctypes.c_void_p),
+        ("kind", ctypes.c_void_p),
+        ("cap", ctypes.c_uint64),
+        ("flip_offsets", ctypes.c_void_p),
+        ("flip_bits", ctypes.c_void_p),
+        ("flip_by", ctypes.c_void_p),
+        ("flip_cap", ctypes.c_uint64),
+        ("nitems", ctypes.c_uint64),
+        ("nbad", ctypes.c_uint64),
+        ("nsalvaged", ctypes.c_uint64),
+        ("nsuspect", ctypes.c_uint64),
+        ("scanned", ctypes.c_uint64),
+        ("ncand", ctypes.c_uint64),
+        ("nflips", ctypes.c_uint64),
+        ("headers_repaired", ctypes.c_uint64),
+        ("items_repaired", ctypes.c_uint64),
+        ("rounds", ctypes.c_uint32),
+        ("complete", ctypes.c_uint32),
     ]
 
 
@@ -106,6 +144,7 @@ PROTOTYPES = {
     "crc32c_repair_items": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _U32, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
     "crc32c_locate_bit": (_U64, [_U32, _U32, _U64]),
     "crc32c_repair_headers": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _PTR, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
+    "crc32c_scrub_pages": (_INT, [_PTR, _U64, _U64, ctypes.POINTER(ScrubOpts), ctypes.POINTER(ScrubOut)]),
     "crc32c_batch_chains": (_INT, [_SPANS, _PTR, _U64, _PTR, _UINT, _PTR]),
     "crc32c_host_alloc": (_PTR, [_SIZE]),
     "crc32c_host_free": (None, [_PTR]),
@@ -123,7 +162,7 @@ PROTOTYPES = {
 # what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
 NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min",
          "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit", "crc32c_repair_headers",
-         "crc32c_triage_pages")
+         "crc32c_triage_pages", "crc32c_scrub_pages")
 
 
 def _load():

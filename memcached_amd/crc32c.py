@@ -17,6 +17,7 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``repair_items`` single-bit damage of item images located by the stored CRC and flipped back
   (``locate_bit``: the same search for one span on the host)
 * ``repair_headers`` a flipped length bit of an item header found among the 42 headers one bit away
+* ``scrub_pages`` triage_pages, repair_headers and repair_items round by round in one call: the final list and a flip log
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
 * ``batch_multi``  host batch split across GPUs by bytes
 
@@ -35,7 +36,7 @@ import numpy as np
 from . import _lib
 from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
 
-# (recover_pages, triage_pages, repair_items, locate_bit and repair_headers are public as well; tests/test_python_face.py pins this list as it
+# (recover_pages, triage_pages, repair_items, locate_bit, repair_headers and scrub_pages are public as well; tests/test_python_face.py pins this list as it
 # stood before them)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
@@ -560,6 +561,67 @@ def repair_headers(buf, item_offsets, region_bytes=0, locate_only=False, stream=
                                     ctypes.byref(nrepaired), ctypes.byref(nbad), flags, side.stream),
           "crc32c_repair_headers")
     return ok, bit, lens, {"nrepaired": int(nrepaired.value), "nbad": int(nbad.value)}
+
+
+def scrub_pages(buf, wbuf_bytes, max_span=0, max_rounds=0, locate_only=False, stream=None, cflags64=False):
+    """A page's whole repair flow in one call (crc32c_scrub_pages):
+    triage_pages, rounds of repair_headers over every kind-0 entry and each
+    piece's walk end, repair_items over the damaged entries and the suspects
+    that overlap nothing proven, and the triage again after every round that
+    repaired something, with the page staged once and the lists kept on the
+    device.
+
+    Returns (offsets, lens, kind, flip_offsets, flip_bits, flip_by, info) for
+    numpy and torch buffers: the final triage list, the log of every bit
+    inverted in the order made (the image's offset, the image's bit index, and
+    CRC32C_SCRUB_BY_HEADER or CRC32C_SCRUB_BY_ITEM), and info = {"rc", "nbad",
+    "nsalvaged", "nsuspect", "scanned", "ncand", "nflips", "headers_repaired",
+    "items_repaired", "rounds", "complete"}.  complete 1: nothing more can be
+    repaired, a second call changes nothing; 0 with rc 0: ``max_rounds`` (0:
+    64) was reached.  rc is CRC32C_OK, or the CRC32C_EWORK / CRC32C_EWALK of
+    the stage that ended the flow (what was repaired before stays repaired and
+    logged); any other status raises.
+
+    ``locate_only`` (host buffers only): ``buf`` is left as it is, the list and
+    the log describe the page as it would be.  A host buffer that is not a
+    writable contiguous uint8 numpy array is accepted only so.  The result
+    arrays are sized as triage_pages sizes them and the log at one flip per
+    256 bytes; a host call that outgrows them is made again (it runs
+    locate-only, and the logged bits are inverted here), a device call that
+    outgrows the list fetches it with triage_pages, and one that outgrows the
+    log returns its first entries (info["nflips"] is exact)."""
+    wbuf_bytes = _wbuf_bytes(wbuf_bytes)
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf, inplace=None if locate_only else
+                              "scrub_pages needs {} (repaired in place) unless locate_only is set")
+    mode = side.flag | _flags(cflags64) | (0 if side.dev and not locate_only else _lib.CRC32C_LOCATE_ONLY)
+    opts = _lib.ScrubOpts(mode, max_span, max_rounds, side.stream)
+    cap = _walk_bound(nbytes, wbuf_bytes)
+    if side.dev:
+        cap = min(nbytes // 1024 + -(-nbytes // wbuf_bytes), cap) + nbytes // (100 * 1024) + 64
+    else:
+        cap += nbytes // 50
+    flip_cap = nbytes // 256 + 64
+    while True:
+        arrays = [side.empty(cap, k) for k in (_U64, _U32, _U8)] + [side.empty(flip_cap, k) for k in (_U64, _U64, _U8)]
+        out = _lib.ScrubOut(*map(_ptr, arrays[:3]), cap, *map(_ptr, arrays[3:]), flip_cap)
+        rc = lib.crc32c_scrub_pages(_ptr(buf), nbytes, wbuf_bytes, ctypes.byref(opts), ctypes.byref(out))
+        if rc not in (_lib.CRC32C_EWORK, _lib.CRC32C_EWALK):
+            check(rc, "crc32c_scrub_pages")
+        if side.dev or (out.nitems <= cap and out.nflips <= flip_cap):
+            break
+        cap, flip_cap = max(cap, out.nitems), max(flip_cap, out.nflips)
+    offs, lens, kind = (a[:min(out.nitems, cap)] for a in arrays[:3])
+    flips = [a[:min(out.nflips, flip_cap)] for a in arrays[3:]]
+    if side.dev and out.nitems > cap and rc == _lib.CRC32C_OK:
+        offs, lens, kind, _ = triage_pages(buf, wbuf_bytes, stream=stream, cflags64=cflags64)
+    if not side.dev and not locate_only:
+        for o, k in zip(flips[0].tolist(), flips[1].tolist()):
+            buf[o + k // 8] ^= 1 << (k % 8)
+    info = {name: int(getattr(out, name)) for name in ("nbad", "nsalvaged", "nsuspect", "scanned", "ncand", "nflips",
+                                                       "headers_repaired", "items_repaired", "rounds", "complete")}
+    info["rc"] = rc
+    return (offs, lens, kind, *flips, info)
 
 
 def locate_bit(crc_computed: int, crc_stored: int, length: int) -> int:

@@ -44,3 +44,4 @@
 #include "k_repair.h"  // crc32c_repair_items: k_repair_count, k_repair_emit, k_repair_search, k_repair_apply
 #include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply
 #include "k_triage.h"  // crc32c_triage_pages: k_triage_pick, k_triage_merge
+#include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_log

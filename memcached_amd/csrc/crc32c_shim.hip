@@ -63,6 +63,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_recover.h"
 #include "shim_repair.h"
 #include "shim_header.h"
+#include "shim_scrub.h"
 
 // Batch C ABI
 extern "C" {
@@ -367,6 +368,11 @@ int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes
                           unsigned flags, void *stream) {
     return repair_headers(base, base_bytes, region_bytes, item_offsets, n, ok, bit, lens, nrepaired, nbad, flags,
                           stream);
+}
+
+int crc32c_scrub_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, const crc32c_scrub_opts *opts,
+                       crc32c_scrub_out *out) {
+    return scrub_pages(base, base_bytes, wbuf_bytes, opts, out);
 }
 
 int crc32c_shard_cuts(const uint32_t *lens, uint32_t len, uint64_t n, int parts, uint64_t *cuts) {

@@ -1,0 +1,197 @@
+// k_scrub.h -- crc32c_scrub_pages: the two list rules a caller of the repair
+// flow ran on the host between crc32c_triage_pages and the repair calls, and
+// the flip log, as kernels over the merged list where k_triage_merge left it
+// (ascending by offset, whole: the scrub sizes its scratch by the list).
+//
+//   k_scrub_headers  the list for crc32c_repair_headers:
+//                    per piece every kind-0 entry, then the piece's walk end --
+//                    the end of its last walked entry (kinds 4 and 6 are no
+//                    walked entries), or the piece's start when it has none --
+//                    when that entry is not kind 0 and 48 bytes of the piece
+//                    remain there;
+//   k_scrub_items    the list for crc32c_repair_items:
+//                    every kind-0 entry with a length, and every suspect that
+//                    ends at or before the next proven entry (kind 1 or 4) and
+//                    starts at or behind the end of the last suspect kept;
+//   k_scrub_log      a repair stage's verdicts compacted into the log, in list
+//                    order.
+// The two list kernels run twice around a k_scan32, as the walk does: one wave
+// per piece, its entries 64 a round.  Both rules are piece-local: a piece's
+// entries are one range of the list, a suspect is a sane candidate and so lies
+// inside its own piece, hence ends at or before any proven entry of a later
+// piece and starts behind any suspect kept in an earlier one.
+#pragma once
+
+#include "k_triage.h"
+
+namespace mcrc_dev {
+
+constexpr uint32_t kScrubLogThreads = 1024;  // k_scrub_log's round
+
+// The merged list as the triage left it (n: all of its entries).
+struct ScrubList {
+    const uint64_t *offs;
+    const uint32_t *lens;
+    const uint8_t *kind;
+    uint64_t n;
+};
+
+__device__ __forceinline__ uint32_t scrub_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+//   EMIT false: cnt[w] = the piece's entries of the header list;
+//   EMIT true:  entry prefix[w] + r is written to out, when below cap.
+template <bool EMIT>
+__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_headers(ScrubList l, uint64_t wbuf, uint64_t base_bytes,
+                                                                   uint64_t nw, uint32_t *cnt, const uint32_t *prefix,
+                                                                   uint64_t *out, uint64_t cap) {
+    MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
+    const uint32_t j = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint64_t w = (uint64_t)blockIdx.x * kWalkWaves + wave; w < nw; w += (uint64_t)gridDim.x * kWalkWaves) {
+        const uint64_t ps = w * wbuf, pe = mcrc::salvage_piece_end(w, wbuf, base_bytes);
+        const uint64_t k0 = sv_lower_bound(l.offs, l.n, ps), k1 = sv_lower_bound(l.offs, l.n, pe);
+        const uint64_t first = EMIT ? prefix[w] : 0;
+        uint64_t end = ps;   // the walk end: behind the last walked entry
+        uint32_t last = 1u;  // that entry's kind (none: as a good one)
+        uint32_t listed = 0;
+        for (uint64_t kk = k0; kk < k1; kk += 64) {
+            const uint64_t i = kk + j;
+            const bool in = i < k1;
+            const uint64_t o = in ? l.offs[i] : 0;
+            const uint32_t len = in ? l.lens[i] : 0u;
+            const uint32_t kd = in ? l.kind[i] : (uint32_t)kKindSalvaged;
+            const bool zero = in && kd == 0u;
+            const unsigned long long zm = __ballot(zero);
+            if (EMIT && zero) {
+                const uint64_t idx = first + listed + scrub_rank(zm);
+                if (idx < cap) out[idx] = o;
+            }
+            listed += (uint32_t)__popcll(zm);
+            const unsigned long long wm = __ballot(in && kd != kKindSalvaged && kd != kKindSuspect);
+            if (wm) {
+                const int src = 63 - __clzll((long long)wm);
+                last = (uint32_t)__shfl((int)kd, src, 64);
+                end = shfl64(o + len, src);
+            }
+        }
+        // (a kind-0 entry is listed as itself; behind a good one every kind-0 entry of the piece lies in front of end)
+        const bool take = last != 0u && end >= ps && end <= pe && pe - end >= 48;
+        if (EMIT) {
+            if (take && j == 0 && first + listed < cap) out[first + listed] = end;
+        } else if (j == 0) {
+            cnt[w] = listed + (uint32_t)take;
+        }
+    }
+}
+
+// The greedy chain of the suspects kept is sequential, but only along the
+// suspects that end in time: the wave goes through those in order, as
+// k_triage_pick goes through the verified candidates.  The next proven entry
+// behind a lane's own is the first one above it in the round's ballot, or the
+// first one of the rounds behind it (`nxt`, looked for once per proven entry:
+// the search resumes where it last ended).
+//   EMIT false: cnt[w] = the piece's entries of the item list;
+//   EMIT true:  entry prefix[w] + r is written to out, when below cap.
+template <bool EMIT>
+__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_items(ScrubList l, uint64_t wbuf, uint64_t base_bytes,
+                                                                 uint64_t nw, uint32_t *cnt, const uint32_t *prefix,
+                                                                 uint64_t *out, uint64_t cap) {
+    MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
+    const uint32_t j = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the lanes above this one, by halves (no 64-bit shift by a register amount)
+    const uint32_t above_lo = j < 32u ? 0xfffffffeu << j : 0u;
+    const uint32_t above_hi = j < 32u ? 0xffffffffu : 0xfffffffeu << (j - 32u);
+    for (uint64_t w = (uint64_t)blockIdx.x * kWalkWaves + wave; w < nw; w += (uint64_t)gridDim.x * kWalkWaves) {
+        const uint64_t ps = w * wbuf, pe = mcrc::salvage_piece_end(w, wbuf, base_bytes);
+        const uint64_t k0 = sv_lower_bound(l.offs, l.n, ps), k1 = sv_lower_bound(l.offs, l.n, pe);
+        const uint64_t first = EMIT ? prefix[w] : 0;
+        uint64_t kept_end = 0;
+        uint64_t nxt_at = k0, nxt = UINT64_MAX;  // the first proven entry at or behind some index <= kk + 64, or k1
+        uint32_t listed = 0;
+        for (uint64_t kk = k0; kk < k1; kk += 64) {
+            const uint64_t i = kk + j;
+            const bool in = i < k1;
+            const uint64_t o = in ? l.offs[i] : 0;
+            const uint32_t len = in ? l.lens[i] : 0u;
+            const uint32_t kd = in ? l.kind[i] : 0u;
+            const bool sus = in && kd == kKindSuspect;
+            if (__ballot(sus) && nxt_at < kk + 64) {
+                nxt_at = k1;
+                nxt = UINT64_MAX;
+                for (uint64_t c = kk + 64; c < k1; c += 64) {
+                    const uint64_t ii = c + j;
+                    const uint32_t k2 = ii < k1 ? l.kind[ii] : 0u;
+                    const unsigned long long m = __ballot(k2 == 1u || k2 == kKindSalvaged);
+                    if (m) {
+                        nxt_at = c + (uint64_t)(__ffsll(m) - 1);
+                        nxt = l.offs[nxt_at];
+                        break;
+                    }
+                }
+            }
+            const unsigned long long pm = __ballot(in && (kd == 1u || kd == kKindSalvaged));
+            const uint32_t plo = (uint32_t)pm & above_lo, phi = (uint32_t)(pm >> 32) & above_hi;
+            const int psrc = plo ? __ffs((int)plo) - 1 : phi ? 32 + __ffs((int)phi) - 1 : -1;
+            const uint64_t pin = shfl64(o, psrc < 0 ? 0 : psrc);
+            const uint64_t next = psrc < 0 ? nxt : pin;
+            bool keep = false;
+            unsigned long long m = __ballot(sus && o + len <= next);
+            while (m) {
+                const int src = __ffsll(m) - 1;
+                m &= m - 1;
+                const uint64_t so = shfl64(o, src);
+                if (so >= kept_end) {
+                    kept_end = so + (uint32_t)__shfl((int)len, src, 64);
+                    keep |= (int)j == src;
+                }
+            }
+            const bool take = keep || (in && kd == 0u && len != 0u);
+            const unsigned long long tm = __ballot(take);
+            if (EMIT && take) {
+                const uint64_t idx = first + listed + scrub_rank(tm);
+                if (idx < cap) out[idx] = o;
+            }
+            listed += (uint32_t)__popcll(tm);
+        }
+        if (!EMIT && j == 0) cnt[w] = listed;
+    }
+}
+
+// The log of one repair stage: entry i of its list with ok[i] = kItemRepaired
+// becomes (list[i], bit[i], by), the r-th such entry at log index at + r when
+// that is below cap.  One workgroup, kScrubLogThreads entries a round (a list
+// is a few entries per damaged image).
+__global__ __launch_bounds__(kScrubLogThreads) void k_scrub_log(const uint64_t *list, const uint8_t *ok,
+                                                                const uint64_t *bit, uint64_t n, uint32_t by,
+                                                                uint64_t at, uint64_t cap, uint64_t *flip_offsets,
+                                                                uint64_t *flip_bits, uint8_t *flip_by) {
+    MCRC_VGPR_FLOOR();
+    __shared__ uint32_t sh[kScrubLogThreads / 64];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t carry = at;
+    for (uint64_t i0 = 0; i0 < n; i0 += kScrubLogThreads) {
+        const uint64_t i = i0 + threadIdx.x;
+        const bool hit = i < n && ok[i] == kItemRepaired;
+        const unsigned long long m = __ballot(hit);
+        if (lane == 0) sh[w] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t k = 0; k < kScrubLogThreads / 64; ++k) {
+            before += k < w ? sh[k] : 0u;
+            all += sh[k];
+        }
+        __syncthreads();
+        const uint64_t idx = carry + before + scrub_rank(m);
+        if (hit && idx < cap) {
+            flip_offsets[idx] = list[i];
+            flip_bits[idx] = bit[i];
+            flip_by[idx] = (uint8_t)by;
+        }
+        carry += all;
+    }
+}
+
+}  // namespace mcrc_dev

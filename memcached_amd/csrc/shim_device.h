@@ -161,6 +161,12 @@ struct Device {
     DevBuf<uint8_t> hd_ok;
     PinBuf<uint64_t> hd_hbit;
     PinBuf<uint32_t> hd_hlens;
+    // crc32c_scrub_pages: the per-piece counts and scan of a repair list, the
+    // list, a list length's pinned word, and a host call's flips of one round
+    DevBuf<uint32_t> sc_cnt, sc_pre;
+    DevBuf<uint64_t> sc_list, sc_foff, sc_fbit;
+    DevBuf<uint8_t> sc_fby;
+    PinBuf<uint32_t> sc_host;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

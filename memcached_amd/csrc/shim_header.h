@@ -21,52 +21,23 @@ static_assert(mcrc::kHeaderBits == CRC32C_HEADER_BITS && mcrc::kHeaderWorkMax ==
 static_assert(mcrc::kHeaderVariants <= 64, "a lane of one wave per variant");
 static_assert(mcrc::kHeaderListMax * mcrc::kHeaderVariants < mcrc::kCountMax, "the candidates' 32-bit scan is exact");
 
-int repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets, uint64_t n,
-                   uint8_t *ok, uint64_t *bit, uint32_t *lens, uint64_t *nrepaired, uint64_t *nbad, unsigned flags,
-                   void *stream) {
-    if (!base || !item_offsets || !ok || !bit || !lens || !nrepaired || !nbad || n > mcrc::kHeaderListMax)
-        return CRC32C_EINVAL;
-    Device *dp = nullptr;
-    int rc = current_device(&dp);
-    if (rc) return rc;
-    Device &d = *dp;
-    *nrepaired = *nbad = 0;
-    if (n == 0) {
-        g_last_kernel_ms = 0.0f;
-        return CRC32C_OK;
-    }
-    const bool dev = flags & CRC32C_DEVICE, locate_only = flags & CRC32C_LOCATE_ONLY;
-    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = dev ? (hipStream_t)stream : d.stream;  // (device: NULL is the default stream)
-    if (!dev) HIP_OK(hipSetDevice(d.id));
-    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
-
-    mcrc_dev::SpanArgs a = item_args(d, base, base_bytes, region_bytes, n, flags);
-    a.offsets = item_offsets;
+// The call's stages over a device-resident buffer and list (a.base, a.offsets,
+// a.n = n >= 1), under a lock and a lease already held: repair_headers below
+// and crc32c_scrub_pages (shim_scrub.h) call it.  The verdicts go to the device
+// arrays d_ok, d_bit and d_lens; `keep`: nothing is written into the buffer.
+// On CRC32C_OK the stream still runs: *counts (pinned) holds [kHdBad] and
+// [kHdRepaired] once it has drained.  CRC32C_EWORK: the stream has drained and
+// nothing was written.
+int header_stages(Device &d, hipStream_t st, const mcrc_dev::SpanArgs &a, uint64_t base_bytes, uint64_t n,
+                  uint8_t *d_ok, uint64_t *d_bit, uint32_t *d_lens, bool keep, unsigned long long **counts) {
+    int rc;
     mcrc_dev::HeaderArgs h{};
     h.cnt = d.hd_cnt.reserve(n * 4);
     h.pre = d.hd_pre.reserve((n + 1) * 4);
     h.ctr = d.hd_ctr.reserve(mcrc_dev::kHdWords * sizeof(unsigned long long));
     unsigned long long *const hc = d.hd_host.reserve(mcrc_dev::kHdWords * sizeof(unsigned long long));
     if (!h.cnt || !h.pre || !h.ctr || !hc) return CRC32C_ENOMEM;
-    uint8_t *d_ok = ok;
-    uint64_t *d_bit = bit;
-    uint32_t *d_lens = lens;
-    if (!dev) {
-        uint8_t *b = d.stage.reserve(base_bytes);
-        uint64_t *o = d.item_offs.reserve(n * 8);
-        d_ok = d.hd_ok.reserve(n);
-        d_bit = d.hd_bit.reserve(n * 8);
-        d_lens = d.hd_lens.reserve(n * 4);
-        if (!b || !o || !d_ok || !d_bit || !d_lens || !d.pin_ok.reserve(n) || !d.hd_hbit.reserve(n * 8) ||
-            !d.hd_hlens.reserve(n * 4))
-            return CRC32C_ENOMEM;
-        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(o, item_offsets, n * 8, hipMemcpyHostToDevice, st));
-        a.base = b;
-        a.offsets = o;
-    }
+    *counts = hc;
 
     // the candidates counted, with their spans' sum for the work bound
     const dim3 grid((unsigned)std::min<uint64_t>((n + mcrc_dev::kHdWaves - 1) / mcrc_dev::kHdWaves,
@@ -104,12 +75,57 @@ int repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes, const
         s.n = nc;
         if ((rc = run_spans(d, s, mcrc::span_route(s, small_max()), st))) return rc;
     }
-    // (a staged buffer is the call's own copy: the host inverts the caller's bits)
     hipLaunchKernelGGL(mcrc_dev::k_header_apply, grid, block, 0, st, a, h, (const uint32_t *)crc, d_ok, d_bit, d_lens,
-                       (uint32_t)(locate_only || !dev));
+                       (uint32_t)keep);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(hc + mcrc_dev::kHdBad, h.ctr + mcrc_dev::kHdBad, 2 * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, st));
+    return CRC32C_OK;
+}
+
+int repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets, uint64_t n,
+                   uint8_t *ok, uint64_t *bit, uint32_t *lens, uint64_t *nrepaired, uint64_t *nbad, unsigned flags,
+                   void *stream) {
+    if (!base || !item_offsets || !ok || !bit || !lens || !nrepaired || !nbad || n > mcrc::kHeaderListMax)
+        return CRC32C_EINVAL;
+    Device *dp = nullptr;
+    int rc = current_device(&dp);
+    if (rc) return rc;
+    Device &d = *dp;
+    *nrepaired = *nbad = 0;
+    if (n == 0) {
+        g_last_kernel_ms = 0.0f;
+        return CRC32C_OK;
+    }
+    const bool dev = flags & CRC32C_DEVICE, locate_only = flags & CRC32C_LOCATE_ONLY;
+    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
+    std::lock_guard<std::mutex> lk(d.mu);
+    hipStream_t st = dev ? (hipStream_t)stream : d.stream;  // (device: NULL is the default stream)
+    if (!dev) HIP_OK(hipSetDevice(d.id));
+    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
+
+    mcrc_dev::SpanArgs a = item_args(d, base, base_bytes, region_bytes, n, flags);
+    a.offsets = item_offsets;
+    uint8_t *d_ok = ok;
+    uint64_t *d_bit = bit;
+    uint32_t *d_lens = lens;
+    if (!dev) {
+        uint8_t *b = d.stage.reserve(base_bytes);
+        uint64_t *o = d.item_offs.reserve(n * 8);
+        d_ok = d.hd_ok.reserve(n);
+        d_bit = d.hd_bit.reserve(n * 8);
+        d_lens = d.hd_lens.reserve(n * 4);
+        if (!b || !o || !d_ok || !d_bit || !d_lens || !d.pin_ok.reserve(n) || !d.hd_hbit.reserve(n * 8) ||
+            !d.hd_hlens.reserve(n * 4))
+            return CRC32C_ENOMEM;
+        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(o, item_offsets, n * 8, hipMemcpyHostToDevice, st));
+        a.base = b;
+        a.offsets = o;
+    }
+    // (a staged buffer is the call's own copy: the host inverts the caller's bits)
+    unsigned long long *hc = nullptr;
+    if ((rc = header_stages(d, st, a, base_bytes, n, d_ok, d_bit, d_lens, locate_only || !dev, &hc))) return rc;
     uint8_t *const h_ok = d.pin_ok.get();
     uint64_t *const h_bit = d.hd_hbit.get();
     uint32_t *const h_lens = d.hd_hlens.get();

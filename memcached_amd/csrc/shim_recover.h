@@ -14,35 +14,23 @@ namespace {
 
 static_assert(mcrc_dev::kKindSalvaged == CRC32C_ITEM_SALVAGED, "the merge writes the header's kind");
 
-int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
-                  uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
-                  uint64_t *nsuspect, bool triage, uint64_t *scanned, uint64_t *ncand, unsigned flags,
-                  void *stream) {
-    if (!base || !nitems || !nbad || !nsalvaged || !wbuf_bytes || (cap && (!offsets || !lens || !kind)) ||
-        (triage && !nsuspect))
-        return CRC32C_EINVAL;
-    Device *dp = nullptr;
-    int rc = current_device(&dp);
-    if (rc) return rc;
-    Device &d = *dp;
-    hipStream_t st = (hipStream_t)stream;
-    const bool dev = flags & CRC32C_DEVICE;
-    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
-    auto done = [&](uint64_t ni, uint64_t nb, uint64_t ns, uint64_t sc, uint64_t nc, int ret, uint64_t nsus = 0) {
-        *nitems = ni;
-        *nbad = nb;
-        *nsalvaged = ns;
-        if (triage) *nsuspect = nsus;
-        if (scanned) *scanned = sc;
-        if (ncand) *ncand = nc;
-        return ret;
-    };
-    const uint64_t nw = (base_bytes + wbuf_bytes - 1) / wbuf_bytes;
-    if (nw == 0) return done(0, 0, 0, 0, 0, CRC32C_OK);
-    if (nw >= 0x7fffffffull) return CRC32C_EINVAL;
-    std::lock_guard<std::mutex> lk(d.mu);
-    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
+// What recover_stages leaves: the counts, the call's status, and the merged
+// list's device arrays (`out`, with the entries written in out.cap).
+struct PageLists {
+    uint64_t total = 0, np = 0, nf = 0, nb = 0, sc = 0, nc = 0;  // walked, picked, found among them, bad, scanned, candidates
+    int ret = CRC32C_OK;  // CRC32C_OK, CRC32C_EWALK or CRC32C_EWORK: the lists are the walk's then
+    mcrc_dev::RecoverOut out{nullptr, nullptr, nullptr, 0};
+};
 
+// The call's stages under a lock and a lease already held: recover_pages below
+// and crc32c_scrub_pages (shim_scrub.h) call it.  base: a device buffer with
+// CRC32C_DEVICE in flags, else a host buffer, which the walk stages.  direct:
+// the device arrays that take the merged list's first direct->cap entries, or
+// nullptr: scratch takes its first cap (UINT64_MAX: the whole list).  Returns
+// with the stream drained.
+int recover_stages(Device &d, hipStream_t st, const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t nw,
+                   bool triage, unsigned flags, const mcrc_dev::RecoverOut *direct, uint64_t cap, PageLists *p) {
+    int rc;
     // the walk and its verify: the lists stay in walk scratch
     mcrc_dev::SpanArgs a;
     mcrc_dev::WalkOut wo;
@@ -82,9 +70,10 @@ int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, ui
     }
 
     // the merge: into the caller's device arrays, or into scratch of the entries a host caller takes
-    const uint64_t most = total + (found ? r.nc : 0), kcap = std::min(cap, most);
-    mcrc_dev::RecoverOut out{offsets, lens, kind, cap};
-    if (!dev && kcap) {
+    const uint64_t most = total + (found ? r.nc : 0), kcap = std::min(direct ? direct->cap : cap, most);
+    mcrc_dev::RecoverOut out{nullptr, nullptr, nullptr, 0};
+    if (direct) out = *direct;
+    if (!direct && kcap) {
         out = mcrc_dev::RecoverOut{d.rc_offs.reserve(kcap * 8), d.rc_lens.reserve(kcap * 4), d.rc_kind.reserve(kcap),
                                    kcap};
         if (!out.offsets || !out.lens || !out.kind) return CRC32C_ENOMEM;
@@ -103,13 +92,57 @@ int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, ui
     }
     HIP_OK(hipStreamSynchronize(st));
     // (triage: h32[0] is the picked entries, found and suspects together, h32[1] the found among them)
-    const uint64_t np = found ? r.h32[0] : 0, nf = triage && found ? r.h32[1] : np, k = std::min(cap, total + np);
+    p->total = total;
+    p->np = found ? r.h32[0] : 0;
+    p->nf = triage && found ? r.h32[1] : p->np;
+    p->nb = nb;
+    p->sc = r.sc;
+    p->nc = r.nc;
+    p->ret = ret;
+    p->out = out;
+    return CRC32C_OK;
+}
+
+int recover_pages(const void *base, uint64_t base_bytes, uint64_t wbuf_bytes, uint64_t *offsets, uint32_t *lens,
+                  uint8_t *kind, uint64_t cap, uint64_t *nitems, uint64_t *nbad, uint64_t *nsalvaged,
+                  uint64_t *nsuspect, bool triage, uint64_t *scanned, uint64_t *ncand, unsigned flags,
+                  void *stream) {
+    if (!base || !nitems || !nbad || !nsalvaged || !wbuf_bytes || (cap && (!offsets || !lens || !kind)) ||
+        (triage && !nsuspect))
+        return CRC32C_EINVAL;
+    Device *dp = nullptr;
+    int rc = current_device(&dp);
+    if (rc) return rc;
+    Device &d = *dp;
+    hipStream_t st = (hipStream_t)stream;
+    const bool dev = flags & CRC32C_DEVICE;
+    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
+    auto done = [&](uint64_t ni, uint64_t nb, uint64_t ns, uint64_t sc, uint64_t nc, int ret, uint64_t nsus = 0) {
+        *nitems = ni;
+        *nbad = nb;
+        *nsalvaged = ns;
+        if (triage) *nsuspect = nsus;
+        if (scanned) *scanned = sc;
+        if (ncand) *ncand = nc;
+        return ret;
+    };
+    const uint64_t nw = (base_bytes + wbuf_bytes - 1) / wbuf_bytes;
+    if (nw == 0) return done(0, 0, 0, 0, 0, CRC32C_OK);
+    if (nw >= 0x7fffffffull) return CRC32C_EINVAL;
+    std::lock_guard<std::mutex> lk(d.mu);
+    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
+
+    const mcrc_dev::RecoverOut mine{offsets, lens, kind, cap};
+    PageLists p;
+    if ((rc = recover_stages(d, st, base, base_bytes, wbuf_bytes, nw, triage, flags, dev ? &mine : nullptr, cap, &p)))
+        return rc;
+    const uint64_t k = std::min(cap, p.total + p.np);
     if (!dev && k) {
-        HIP_OK(hipMemcpy(offsets, out.offsets, k * 8, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(lens, out.lens, k * 4, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(kind, out.kind, k, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(offsets, p.out.offsets, k * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(lens, p.out.lens, k * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(kind, p.out.kind, k, hipMemcpyDeviceToHost));
     }
-    return done(total + np, nb, nf, r.sc, r.nc, ret, np - nf);
+    return done(p.total + p.np, p.nb, p.nf, p.sc, p.nc, p.ret, p.np - p.nf);
 }
 
 }  // namespace

@@ -23,33 +23,22 @@ static_assert(mcrc::kRepairSpanMax == CRC32C_REPAIR_SPAN_MAX && mcrc::kRepairSpa
               "repair_geom.h restates the header's constants");
 static_assert(32 + 8 * (uint64_t)CRC32C_REPAIR_SPAN_MAX < mcrc::kRepairOrder, "a located position is unique");
 
-int repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets, uint64_t n,
-                 uint32_t max_span, uint8_t *ok, uint64_t *bit, uint64_t *nrepaired, uint64_t *nbad, unsigned flags,
-                 void *stream) {
-    if (!base || !item_offsets || !ok || !bit || !nrepaired || !nbad || max_span > CRC32C_REPAIR_SPAN_MAX)
-        return CRC32C_EINVAL;
-    Device *dp = nullptr;
-    int rc = current_device(&dp);
-    if (rc) return rc;
-    Device &d = *dp;
-    *nrepaired = *nbad = 0;
-    if (n == 0) return CRC32C_OK;
-    const bool dev = flags & CRC32C_DEVICE, locate_only = flags & CRC32C_LOCATE_ONLY;
-    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
-    // (k_small, or the planned path: K5's stamps go into the images themselves)
-    const mcrc::ItemRoute route = mcrc::item_route(n, base_bytes, small_max(), false);
-    if (route == mcrc::ItemRoute::invalid) return CRC32C_EINVAL;
-    std::lock_guard<std::mutex> lk(d.mu);
-    hipStream_t st = dev ? (hipStream_t)stream : d.stream;  // (device: NULL is the default stream)
-    if (!dev) HIP_OK(hipSetDevice(d.id));
-    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
-
-    mcrc_dev::SpanArgs a = item_args(d, base, base_bytes, region_bytes, n, flags);
-    a.offsets = item_offsets;
+// The call's stages over a device-resident buffer and list (a.base, a.offsets,
+// a.n = n >= 1, route: item_route's for them), under a lock and a lease already
+// held: repair_items below and crc32c_scrub_pages (shim_scrub.h) call it.  The
+// verdicts go to the device arrays d_ok and d_bit; `keep`: nothing is written
+// into the buffer.  On CRC32C_OK the stream still runs: *counts (pinned) holds
+// [kRpBad] and [kRpRepaired] once it has drained, and with *searched the
+// search's time lies between ev0 and ev1.  CRC32C_EWORK: the stream has
+// drained and nothing was written.
+int item_stages(Device &d, hipStream_t st, const mcrc_dev::SpanArgs &a, uint64_t base_bytes, uint64_t n,
+                mcrc::ItemRoute route, uint32_t max_span, uint8_t *d_ok, uint64_t *d_bit, bool keep,
+                unsigned long long **counts, bool *searched) {
+    int rc;
     mcrc_dev::RepairArgs r{};
     r.max_span = max_span ? max_span : CRC32C_REPAIR_SPAN_DEFAULT;
-    r.ok = ok;
-    r.bit = bit;
+    r.ok = d_ok;
+    r.bit = d_bit;
     uint32_t *const crc = d.rp_crc.reserve(n * 4);
     r.lcnt = d.rp_lcnt.reserve(n * 4);
     r.ccnt = d.rp_ccnt.reserve(n * 4);
@@ -58,18 +47,9 @@ int repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const u
     unsigned long long *const h = d.rp_host.reserve((mcrc_dev::kRpWords + 1) * sizeof(unsigned long long));
     if (!crc || !r.lcnt || !r.ccnt || !lpre || !cpre || !r.ctr || !h) return CRC32C_ENOMEM;
     r.crc = crc;
+    *counts = h;
+    *searched = false;
     uint32_t *const h32 = (uint32_t *)(h + mcrc_dev::kRpWords);  // the two scans' totals
-    if (!dev) {
-        uint8_t *b = d.stage.reserve(base_bytes);
-        uint64_t *o = d.item_offs.reserve(n * 8);
-        r.ok = d.rp_ok.reserve(n);
-        r.bit = d.rp_bit.reserve(n * 8);
-        if (!b || !o || !r.ok || !r.bit || !d.pin_ok.reserve(n) || !d.rp_hbit.reserve(n * 8)) return CRC32C_ENOMEM;
-        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(o, item_offsets, n * 8, hipMemcpyHostToDevice, st));
-        a.base = b;
-        a.offsets = o;
-    }
 
     // the images' CRCs, into scratch
     mcrc_dev::SpanArgs c = a;
@@ -108,22 +88,65 @@ int repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const u
                            (const mcrc_dev::RepairRec *)recs, (const uint32_t *)first, nl, nchunks,
                            (const uint32_t *)d.xpow, found);
         HIP_OK(hipEventRecord(d.ev1, st));
-        // (a staged buffer is the call's own copy: the host inverts the caller's bits)
         hipLaunchKernelGGL(mcrc_dev::k_repair_apply, dim3((unsigned)mcrc::final_grid(nl)), dim3(256), 0, st, a, r,
-                           (const mcrc_dev::RepairRec *)recs, (const uint32_t *)found, nl,
-                           (uint32_t)(locate_only || !dev));
+                           (const mcrc_dev::RepairRec *)recs, (const uint32_t *)found, nl, (uint32_t)keep);
         HIP_OK(hipGetLastError());
+        *searched = true;
     }
     HIP_OK(hipMemcpyAsync(h + mcrc_dev::kRpBad, r.ctr + mcrc_dev::kRpBad, 2 * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, st));
+    return CRC32C_OK;
+}
+
+int repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets, uint64_t n,
+                 uint32_t max_span, uint8_t *ok, uint64_t *bit, uint64_t *nrepaired, uint64_t *nbad, unsigned flags,
+                 void *stream) {
+    if (!base || !item_offsets || !ok || !bit || !nrepaired || !nbad || max_span > CRC32C_REPAIR_SPAN_MAX)
+        return CRC32C_EINVAL;
+    Device *dp = nullptr;
+    int rc = current_device(&dp);
+    if (rc) return rc;
+    Device &d = *dp;
+    *nrepaired = *nbad = 0;
+    if (n == 0) return CRC32C_OK;
+    const bool dev = flags & CRC32C_DEVICE, locate_only = flags & CRC32C_LOCATE_ONLY;
+    if (dev && !device_range_ok(base, base_bytes)) return CRC32C_EINVAL;
+    // (k_small, or the planned path: K5's stamps go into the images themselves)
+    const mcrc::ItemRoute route = mcrc::item_route(n, base_bytes, small_max(), false);
+    if (route == mcrc::ItemRoute::invalid) return CRC32C_EINVAL;
+    std::lock_guard<std::mutex> lk(d.mu);
+    hipStream_t st = dev ? (hipStream_t)stream : d.stream;  // (device: NULL is the default stream)
+    if (!dev) HIP_OK(hipSetDevice(d.id));
+    Lease lease(d, st, !dev);  // (host: every exit drains st, the copies read and write the caller's memory)
+
+    mcrc_dev::SpanArgs a = item_args(d, base, base_bytes, region_bytes, n, flags);
+    a.offsets = item_offsets;
+    uint8_t *d_ok = ok;
+    uint64_t *d_bit = bit;
+    if (!dev) {
+        uint8_t *b = d.stage.reserve(base_bytes);
+        uint64_t *o = d.item_offs.reserve(n * 8);
+        d_ok = d.rp_ok.reserve(n);
+        d_bit = d.rp_bit.reserve(n * 8);
+        if (!b || !o || !d_ok || !d_bit || !d.pin_ok.reserve(n) || !d.rp_hbit.reserve(n * 8)) return CRC32C_ENOMEM;
+        HIP_OK(hipMemcpyAsync(b, base, base_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(o, item_offsets, n * 8, hipMemcpyHostToDevice, st));
+        a.base = b;
+        a.offsets = o;
+    }
+    // (a staged buffer is the call's own copy: the host inverts the caller's bits)
+    unsigned long long *h = nullptr;
+    bool searched = false;
+    if ((rc = item_stages(d, st, a, base_bytes, n, route, max_span, d_ok, d_bit, locate_only || !dev, &h, &searched)))
+        return rc;
     uint8_t *const h_ok = d.pin_ok.get();
     uint64_t *const h_bit = d.rp_hbit.get();
     if (!dev) {
-        HIP_OK(hipMemcpyAsync(h_ok, r.ok, n, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_bit, r.bit, n * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_ok, d_ok, n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(h_bit, d_bit, n * 8, hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));
-    if (nl) (void)hipEventElapsedTime(&g_last_kernel_ms, d.ev0, d.ev1);  // (crc32c_last_kernel_ms: the search)
+    if (searched) (void)hipEventElapsedTime(&g_last_kernel_ms, d.ev0, d.ev1);  // (crc32c_last_kernel_ms: the search)
     if (!dev) {
         memcpy(ok, h_ok, n);
         memcpy(bit, h_bit, n * 8);
