@@ -609,6 +609,42 @@ int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes
  *         i repaired nothing: complete = 1, stop (T describes the page);
  *         log its flips, one more round, T = triage, stop at max_rounds.
  *
+ * CRC32C_SCRUB_GAPS in opts->mode (opt-in; with the bit clear the call is
+ * exactly the above) changes how the two lists are built and nothing else.
+ * An image with one flipped length bit, or one flipped bit of its final CRLF,
+ * behind a header that ended its wbuf's walk is no candidate of the scan (its
+ * end is wrong, or it has no CRLF), so T never names its offset.  But extstore
+ * packs images back to back: it starts where the image in front of it ends,
+ * and when that one is proven, its end is the offset nobody names.
+ *
+ *   gap_starts(T): for every kind-4 entry (o, len) of T, e = o + len, when e
+ *     is the offset of no entry of T of any kind and at least 48 bytes of o's
+ *     piece remain at e; ascending, each once.  (The end of a kind-1 entry
+ *     needs no rule: it is the next walked entry or the piece's walk end,
+ *     which header_list has.)
+ *   header_list'(T): header_list(T) and gap_starts(T) in one ascending list,
+ *     each offset once.
+ *   item_list'(T): item_list applied to T with every gap start g whose header
+ *     is sane (as crc32c_verify_items judges it with region_bytes =
+ *     wbuf_bytes; nt its ITEM_ntotal) merged in by offset as a suspect of
+ *     length nt: kept when it ends at or before the next kind-1 or kind-4
+ *     entry and starts at or behind the end of the last suspect or gap start
+ *     kept.  A gap start that is not sane is not listed for the items.
+ *
+ * The loop, the round count, the log, complete, max_rounds,
+ * CRC32C_LOCATE_ONLY, the host staging, the error codes and the fixpoint
+ * property are unchanged: a header repaired at a gap start is logged with
+ * CRC32C_SCRUB_BY_HEADER, an item repaired there with CRC32C_SCRUB_BY_ITEM.
+ * The next triage finds a repaired gap image as kind 4, so its end is the
+ * next gap start: a run of k consecutive such images takes k rounds.  An
+ * image directly behind the dead header itself stays lost: nothing proven
+ * ends where it starts.  The rule adds no evidence and weakens none: each
+ * listed header still costs 42 * 2^-32 and each listed item (8 nt - 224) /
+ * 2^32, and at most nsalvaged more offsets are listed per round.  The item
+ * rule reads the header at a gap start, where at least 48 bytes of the piece
+ * remain (as the walk reads a header: the 16-byte granules of its bytes
+ * 28..43).  The other entry points ignore the bit.
+ *
  * Outputs.  offsets / lens / kind take the first min(cap, nitems) entries of
  * the last T, and nitems, nbad, nsalvaged, nsuspect, scanned and ncand are
  * its counts, all as crc32c_triage_pages reports them.  The log has one entry
@@ -654,13 +690,16 @@ int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes
  * list 13 B (the whole list stays on the device, not its first cap entries);
  * per piece 8 B of count and scan; per entry of a repair list 8 B of offset
  * and the repair calls' 9 B (items) or 13 B (headers) of verdicts; a host
- * call: the staged page and 17 B per flip of a round. */
+ * call: the staged page and 17 B per flip of a round.  With
+ * CRC32C_SCRUB_GAPS: 12 B per gap start, and where a triage has any, 14 B per
+ * entry of the merged list and its gap starts together. */
 #define CRC32C_SCRUB_ROUNDS_DEFAULT 64
 #define CRC32C_SCRUB_BY_HEADER 1 /* flip_by[]: made by the crc32c_repair_headers stage */
 #define CRC32C_SCRUB_BY_ITEM 2   /* flip_by[]: made by the crc32c_repair_items stage */
+#define CRC32C_SCRUB_GAPS 0x40u  /* crc32c_scrub_opts.mode: list the gap starts too (above); other calls ignore it */
 
 typedef struct crc32c_scrub_opts { /* NULL: all zero */
-    uint32_t mode;       /* CRC32C_DEVICE | CRC32C_CFLAGS64 | CRC32C_LOCATE_ONLY; other bits ignored */
+    uint32_t mode;       /* CRC32C_DEVICE | CRC32C_CFLAGS64 | CRC32C_LOCATE_ONLY | CRC32C_SCRUB_GAPS; others ignored */
     uint32_t max_span;   /* crc32c_repair_items' max_span, same meaning, same CRC32C_EINVAL */
     uint32_t max_rounds; /* 0: CRC32C_SCRUB_ROUNDS_DEFAULT */
     void *stream;

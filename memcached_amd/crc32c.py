@@ -34,7 +34,8 @@ import operator
 import numpy as np
 
 from . import _lib
-from ._lib import CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, Crc32cError, check, lib
+from ._lib import (CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, CRC32C_SCRUB_GAPS, Crc32cError, check,
+                   lib)
 
 # (recover_pages, triage_pages, repair_items, locate_bit, repair_headers and scrub_pages are public as well; tests/test_python_face.py pins this list as it
 # stood before them)
@@ -563,7 +564,8 @@ def repair_headers(buf, item_offsets, region_bytes=0, locate_only=False, stream=
     return ok, bit, lens, {"nrepaired": int(nrepaired.value), "nbad": int(nbad.value)}
 
 
-def scrub_pages(buf, wbuf_bytes, max_span=0, max_rounds=0, locate_only=False, stream=None, cflags64=False):
+def scrub_pages(buf, wbuf_bytes, max_span=0, max_rounds=0, locate_only=False, stream=None, cflags64=False,
+                gaps=False):
     """A page's whole repair flow in one call (crc32c_scrub_pages):
     triage_pages, rounds of repair_headers over every kind-0 entry and each
     piece's walk end, repair_items over the damaged entries and the suspects
@@ -589,12 +591,18 @@ def scrub_pages(buf, wbuf_bytes, max_span=0, max_rounds=0, locate_only=False, st
     256 bytes; a host call that outgrows them is made again (it runs
     locate-only, and the logged bits are inverted here), a device call that
     outgrows the list fetches it with triage_pages, and one that outgrows the
-    log returns its first entries (info["nflips"] is exact)."""
+    log returns its first entries (info["nflips"] is exact).
+
+    ``gaps`` sets CRC32C_SCRUB_GAPS: the end of every image found (kind 4)
+    that is no entry's offset is handed to both repair stages as well, so an
+    image with one flipped length or CRLF bit directly behind a proven one
+    comes back, one such image per round."""
     wbuf_bytes = _wbuf_bytes(wbuf_bytes)
     side = _side(buf, stream)
     buf, nbytes = side.buffer(buf, inplace=None if locate_only else
                               "scrub_pages needs {} (repaired in place) unless locate_only is set")
     mode = side.flag | _flags(cflags64) | (0 if side.dev and not locate_only else _lib.CRC32C_LOCATE_ONLY)
+    mode |= CRC32C_SCRUB_GAPS if gaps else 0
     opts = _lib.ScrubOpts(mode, max_span, max_rounds, side.stream)
     cap = _walk_bound(nbytes, wbuf_bytes)
     if side.dev:

@@ -20,6 +20,26 @@
 // entries are one range of the list, a suspect is a sane candidate and so lies
 // inside its own piece, hence ends at or before any proven entry of a later
 // piece and starts behind any suspect kept in an earlier one.
+//
+// CRC32C_SCRUB_GAPS (the contract's gap_starts, header_list' and item_list'):
+//   k_scrub_gaps          the end of every kind-4 entry that is no entry's
+//                         offset and has 48 bytes of its piece behind it, as
+//                         entries of a list of their own: the offset and the
+//                         ITEM_ntotal of the header there when it is sane,
+//                         else 0;
+//   k_scrub_gap_merge     the merged list and the gap entries in one second
+//                         list, ascending (a gap start is no entry's offset:
+//                         no ties), with two kind arrays: a gap entry is
+//                         kKindGap for the headers, and for the items
+//                         kKindSuspect when it has a length, else kKindGap;
+//   k_scrub_headers_gaps  k_scrub_headers over the second list: a gap entry is
+//                         listed as a kind-0 entry is, and the walk end takes
+//                         its place in front of the gap starts behind it.
+// k_scrub_items runs over the second list as it is: a gap entry with a length
+// goes through its filter as the suspect its kind says, one without is of no
+// kind it takes.  (k_scrub_headers_gaps is a kernel of its own: the older
+// kernels' instruction streams are kept as they are, as for k_triage_pick.)
+// A gap start lies in its entry's piece, so both rules stay piece-local.
 #pragma once
 
 #include "k_triage.h"
@@ -27,6 +47,7 @@
 namespace mcrc_dev {
 
 constexpr uint32_t kScrubLogThreads = 1024;  // k_scrub_log's round
+constexpr uint8_t kKindGap = 7;              // a gap start in the second list (never leaves the device)
 
 // The merged list as the triage left it (n: all of its entries).
 struct ScrubList {
@@ -157,6 +178,133 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_items(ScrubList l, ui
             listed += (uint32_t)__popcll(tm);
         }
         if (!EMIT && j == 0) cnt[w] = listed;
+    }
+}
+
+// The gap starts of the merged list l (the triage's; a: the page).  One wave
+// per piece, its entries 64 a round.  e, the end of a kind-4 entry, is a gap
+// start when 48 bytes of the piece remain there and no entry of the piece
+// starts at e: a lower bound over the piece's entries, not a look at the next
+// one (a walked kind-0 entry can lie inside a salvaged image's bytes).  The
+// kind-4 entries of a piece are disjoint and ascend, so their ends do.
+//   EMIT false: cnt[w] = the piece's gap starts;
+//   EMIT true:  gap start prefix[w] + r is written to g, when below g.cap: its
+//               offset, and the ITEM_ntotal of the header at e when that is
+//               sane (parse_hdr reads the 16-byte granules of bytes 28..43 of
+//               the 48 that remain), else 0.  (g.kind is not written.)
+template <bool EMIT>
+__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_gaps(SpanArgs a, ScrubList l, uint64_t nw, uint32_t *cnt,
+                                                                const uint32_t *prefix, RecoverOut g) {
+    MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
+    const uint32_t j = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint64_t w = (uint64_t)blockIdx.x * kWalkWaves + wave; w < nw; w += (uint64_t)gridDim.x * kWalkWaves) {
+        const uint64_t ps = w * a.region, pe = mcrc::salvage_piece_end(w, a.region, a.base_bytes);
+        const uint64_t k0 = sv_lower_bound(l.offs, l.n, ps), k1 = sv_lower_bound(l.offs, l.n, pe);
+        const uint64_t first = EMIT ? prefix[w] : 0;
+        uint32_t listed = 0;
+        for (uint64_t kk = k0; kk < k1; kk += 64) {
+            const uint64_t i = kk + j;
+            const bool in = i < k1;
+            const uint64_t e = in ? l.offs[i] + l.lens[i] : 0;
+            bool gap = in && l.kind[i] == kKindSalvaged && e > ps && e <= pe && pe - e >= 48;
+            if (gap) {
+                const uint64_t x = k0 + sv_lower_bound(l.offs + k0, k1 - k0, e);
+                gap = !(x < k1 && l.offs[x] == e);
+            }
+            const unsigned long long gm = __ballot(gap);
+            if (EMIT && gap) {
+                const uint64_t idx = first + listed + scrub_rank(gm);
+                if (idx < g.cap) {
+                    const ItemHdr h = parse_hdr(a.base + e);
+                    g.offsets[idx] = e;
+                    g.lens[idx] = item_desc(a, e, h, true).sane ? (uint32_t)h.ntotal(a.cfl) : 0u;
+                }
+            }
+            listed += (uint32_t)__popcll(gm);
+        }
+        if (!EMIT && j == 0) cnt[w] = listed;
+    }
+}
+
+// The second list: l's entries and the ng gap entries (goffs, glens),
+// ascending.  An entry's place is its own index plus the other list's entries
+// below it.  out.kind is the headers' kind array, ikind the items'.
+__global__ __launch_bounds__(256) void k_scrub_gap_merge(ScrubList l, const uint64_t *goffs, const uint32_t *glens,
+                                                         uint64_t ng, RecoverOut out, uint8_t *ikind) {
+    MCRC_VGPR_FLOOR();
+    for (uint64_t t = blockIdx.x * 256ull + threadIdx.x; t < l.n + ng; t += gridDim.x * 256ull) {
+        const bool own = t < l.n;
+        const uint64_t i = own ? t : t - l.n;
+        const uint64_t o = own ? l.offs[i] : goffs[i];
+        const uint64_t at = i + (own ? sv_lower_bound(goffs, ng, o) : sv_lower_bound(l.offs, l.n, o));
+        if (at >= out.cap) continue;
+        const uint32_t len = own ? l.lens[i] : glens[i];
+        out.offsets[at] = o;
+        out.lens[at] = len;
+        out.kind[at] = own ? l.kind[i] : kKindGap;
+        ikind[at] = own ? l.kind[i] : len ? kKindSuspect : kKindGap;
+    }
+}
+
+// k_scrub_headers over the second list.  A gap entry is listed as a kind-0
+// entry is and is no walked entry.  The walk end lies in front of the gap
+// starts behind it, so it is found first, in a pass over the kinds; the
+// listing pass then leaves its place free (`below` entries in front of it) and
+// moves the entries behind it up by one.  A walk end at which a gap entry
+// stands is listed once, as that entry.
+//   EMIT false: cnt[w] = the piece's entries of the header list;
+//   EMIT true:  entry prefix[w] + r is written to out, when below cap.
+template <bool EMIT>
+__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_headers_gaps(ScrubList l, uint64_t wbuf, uint64_t base_bytes,
+                                                                        uint64_t nw, uint32_t *cnt,
+                                                                        const uint32_t *prefix, uint64_t *out,
+                                                                        uint64_t cap) {
+    MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
+    const uint32_t j = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint64_t w = (uint64_t)blockIdx.x * kWalkWaves + wave; w < nw; w += (uint64_t)gridDim.x * kWalkWaves) {
+        const uint64_t ps = w * wbuf, pe = mcrc::salvage_piece_end(w, wbuf, base_bytes);
+        const uint64_t k0 = sv_lower_bound(l.offs, l.n, ps), k1 = sv_lower_bound(l.offs, l.n, pe);
+        const uint64_t first = EMIT ? prefix[w] : 0;
+        uint64_t end = ps;   // the walk end: behind the last walked entry
+        uint32_t last = 1u;  // that entry's kind (none: as a good one)
+        for (uint64_t kk = k0; kk < k1; kk += 64) {
+            const uint64_t i = kk + j;
+            const bool in = i < k1;
+            const uint32_t kd = in ? l.kind[i] : (uint32_t)kKindSalvaged;
+            const unsigned long long wm = __ballot(in && kd != kKindSalvaged && kd != kKindSuspect && kd != kKindGap);
+            if (wm) {
+                const int src = 63 - __clzll((long long)wm);
+                last = (uint32_t)__shfl((int)kd, src, 64);
+                end = shfl64(in ? l.offs[i] + l.lens[i] : 0, src);
+            }
+        }
+        bool take = last != 0u && end >= ps && end <= pe && pe - end >= 48;
+        if (take) {
+            const uint64_t x = k0 + sv_lower_bound(l.offs + k0, k1 - k0, end);
+            take = !(x < k1 && l.offs[x] == end && l.kind[x] == kKindGap);
+        }
+        uint32_t listed = 0, below = 0;
+        for (uint64_t kk = k0; kk < k1; kk += 64) {
+            const uint64_t i = kk + j;
+            const bool in = i < k1;
+            const uint64_t o = in ? l.offs[i] : 0;
+            const uint32_t kd = in ? l.kind[i] : (uint32_t)kKindSalvaged;
+            const bool zero = in && (kd == 0u || kd == kKindGap);
+            const unsigned long long zm = __ballot(zero);
+            if (EMIT && zero) {
+                const uint64_t idx = first + listed + scrub_rank(zm) + (take && o > end ? 1u : 0u);
+                if (idx < cap) out[idx] = o;
+            }
+            listed += (uint32_t)__popcll(zm);
+            below += (uint32_t)__popcll(__ballot(zero && o < end));
+        }
+        if (EMIT) {
+            if (take && j == 0 && first + below < cap) out[first + below] = end;
+        } else if (j == 0) {
+            cnt[w] = listed + (uint32_t)take;
+        }
     }
 }
 

@@ -167,6 +167,10 @@ struct Device {
     DevBuf<uint64_t> sc_list, sc_foff, sc_fbit;
     DevBuf<uint8_t> sc_fby;
     PinBuf<uint32_t> sc_host;
+    // ... with CRC32C_SCRUB_GAPS: the gap entries, and the merged list with them (the second list, a kind array per repair stage)
+    DevBuf<uint64_t> sc_goffs, sc_moffs;
+    DevBuf<uint32_t> sc_glens, sc_mlens;
+    DevBuf<uint8_t> sc_mkind, sc_mikind;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

@@ -15,6 +15,15 @@
 // count and scan; per repair-list entry 8 B of offset, and the verdicts in
 // the repair calls' own host-route scratch (hd_ok, hd_bit, hd_lens; rp_ok,
 // rp_bit); a host call: the staged page and 17 B per flip of a round.
+// CRC32C_SCRUB_GAPS (opts->mode): after each triage the gap starts are counted
+// once (one count, 4 B, crosses the link); where there are any, they are
+// emitted and merged with the triage's list into a second list, and both
+// repair lists of that T are built from it (the headers' by
+// k_scrub_headers_gaps).  With none, or with the bit clear, the launches are
+// the ones above (with the bit set, one count launch, one scan and one 4 B
+// copy more per triage).  Scratch (grow-only): 12 B per gap entry (offset and
+// length; the kind is written by the merge), and 14 B per entry of the second
+// list (offset, length and a kind array per repair stage).
 #pragma once
 
 namespace {
@@ -31,6 +40,11 @@ struct ScrubRun {
     crc32c_scrub_out *o;  // the caller's arrays
     uint32_t *h32 = nullptr;
     uint64_t *list = nullptr;  // the repair list in use
+    bool gaps = false;         // CRC32C_SCRUB_GAPS
+    bool gaps_known = false;   // of the T in hand: ng and, when ng != 0, the second list
+    uint64_t ng = 0;
+    mcrc_dev::ScrubList second{nullptr, nullptr, nullptr, 0};  // (kind: the headers')
+    const uint8_t *second_ikind = nullptr;                       // the items' kind array of it
     uint64_t nflips = 0;
     std::vector<uint64_t> foff, fbit;  // a host call's log
     std::vector<uint8_t> fby;
@@ -38,21 +52,64 @@ struct ScrubRun {
     int triage(PageLists *t, float *ms) {
         const int rc = recover_stages(d, st, page, base_bytes, wbuf_bytes, nw, true, flags, nullptr, UINT64_MAX, t);
         *ms = g_last_kernel_ms;
+        gaps_known = false;
         return rc;
+    }
+
+    // gap_starts(T), and T with them as the second list
+    int gap_list(const mcrc_dev::ScrubList &l) {
+        gaps_known = true;
+        ng = 0;
+        if (l.n == 0) return CRC32C_OK;  // (no kind-4 entry)
+        uint32_t *cnt = d.sc_cnt.reserve(nw * 4), *pre = d.sc_pre.reserve((nw + 1) * 4);
+        if (!cnt || !pre) return CRC32C_ENOMEM;
+        const mcrc_dev::SpanArgs a = item_args(d, page, base_bytes, wbuf_bytes, 0, flags);
+        const dim3 grid(mcrc::walk_grid(nw)), block(64 * mcrc_dev::kWalkWaves);
+        hipLaunchKernelGGL(mcrc_dev::k_scrub_gaps<false>, grid, block, 0, st, a, l, nw, cnt, (const uint32_t *)nullptr,
+                           mcrc_dev::RecoverOut{nullptr, nullptr, nullptr, 0});
+        hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw, pre);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(h32, pre + nw, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if ((ng = *h32) == 0) return CRC32C_OK;
+        const uint64_t n2 = l.n + ng;
+        const mcrc_dev::RecoverOut g{d.sc_goffs.reserve(ng * 8), d.sc_glens.reserve(ng * 4), nullptr, ng};
+        const mcrc_dev::RecoverOut m{d.sc_moffs.reserve(n2 * 8), d.sc_mlens.reserve(n2 * 4), d.sc_mkind.reserve(n2),
+                                     n2};
+        uint8_t *ikind = d.sc_mikind.reserve(n2);
+        if (!g.offsets || !g.lens || !m.offsets || !m.lens || !m.kind || !ikind) return CRC32C_ENOMEM;
+        hipLaunchKernelGGL(mcrc_dev::k_scrub_gaps<true>, grid, block, 0, st, a, l, nw, (uint32_t *)nullptr,
+                           (const uint32_t *)pre, g);
+        const uint64_t mgrid = std::min<uint64_t>((n2 + 255) / 256, 2048);
+        hipLaunchKernelGGL(mcrc_dev::k_scrub_gap_merge, dim3((unsigned)mgrid), dim3(256), 0, st, l,
+                           (const uint64_t *)g.offsets, (const uint32_t *)g.lens, ng, m, ikind);
+        HIP_OK(hipGetLastError());
+        second = mcrc_dev::ScrubList{m.offsets, m.lens, m.kind, n2};
+        second_ikind = ikind;
+        return CRC32C_OK;
     }
 
     // header_list(T) or item_list(T) into `list`; *n: its length
     template <bool ITEMS>
     int build(const PageLists &t, uint64_t *n) {
-        const mcrc_dev::ScrubList l{t.out.offsets, t.out.lens, t.out.kind, t.total + t.np};
+        mcrc_dev::ScrubList l{t.out.offsets, t.out.lens, t.out.kind, t.total + t.np};
+        if (gaps && !gaps_known) {
+            const int rc = gap_list(l);
+            if (rc) return rc;
+        }
+        const bool g = gaps && ng != 0;  // (the lists of the second list)
+        if (g) l = second;
+        if (g && ITEMS) l.kind = second_ikind;
         uint32_t *cnt = d.sc_cnt.reserve(nw * 4), *pre = d.sc_pre.reserve((nw + 1) * 4);
         if (!cnt || !pre) return CRC32C_ENOMEM;
         const dim3 grid(mcrc::walk_grid(nw)), block(64 * mcrc_dev::kWalkWaves);
         auto launch = [&](auto kern, uint32_t *c, const uint32_t *p, uint64_t *out, uint64_t cap) {
             hipLaunchKernelGGL(kern, grid, block, 0, st, l, wbuf_bytes, base_bytes, nw, c, p, out, cap);
         };
-        if (ITEMS) launch(mcrc_dev::k_scrub_items<false>, cnt, nullptr, nullptr, 0);
-        else launch(mcrc_dev::k_scrub_headers<false>, cnt, nullptr, nullptr, 0);
+        using namespace mcrc_dev;
+        const auto count = ITEMS ? k_scrub_items<false> : g ? k_scrub_headers_gaps<false> : k_scrub_headers<false>;
+        const auto emit = ITEMS ? k_scrub_items<true> : g ? k_scrub_headers_gaps<true> : k_scrub_headers<true>;
+        launch(count, cnt, nullptr, nullptr, 0);
         hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw, pre);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(h32, pre + nw, 4, hipMemcpyDeviceToHost, st));
@@ -60,8 +117,7 @@ struct ScrubRun {
         *n = *h32;
         if (*n == 0) return CRC32C_OK;
         if (!(list = d.sc_list.reserve(*n * 8))) return CRC32C_ENOMEM;
-        if (ITEMS) launch(mcrc_dev::k_scrub_items<true>, nullptr, pre, list, *n);
-        else launch(mcrc_dev::k_scrub_headers<true>, nullptr, pre, list, *n);
+        launch(emit, nullptr, pre, list, *n);
         HIP_OK(hipGetLastError());
         return CRC32C_OK;
     }
@@ -192,6 +248,7 @@ int scrub_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, const crc3
 
     ScrubRun r{d, st, (uint8_t *)base, base_bytes, wbuf_bytes, nw,
                (unsigned)CRC32C_DEVICE | (op.mode & (unsigned)CRC32C_CFLAGS64), dev, out};
+    r.gaps = op.mode & CRC32C_SCRUB_GAPS;
     if (!(r.h32 = d.sc_host.reserve(4))) return CRC32C_ENOMEM;
     if (!dev) {  // the one staging of the page
         if (!(r.page = d.stage.reserve(base_bytes))) return CRC32C_ENOMEM;
