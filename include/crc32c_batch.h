@@ -39,6 +39,10 @@
  *                          mismatch, the stored CRC names it; it is flipped back
  *                          and the image proven again.  crc32c_locate_bit is the
  *                          same search for one span on the host (no GPU).
+ *   crc32c_repair_bytes    the images whose damage is several bits of one byte:
+ *                          the same search names the byte and its XOR mask, at 32
+ *                          times the one-bit rule's false-repair odds
+ *                          (crc32c_locate_byte: one span on the host).
  *   crc32c_repair_headers  the one image per damaged header that those calls still
  *                          lose: a flipped bit of nbytes, nkey or the two it_flags
  *                          bits that decide ITEM_ntotal moves the image's end, and
@@ -495,6 +499,107 @@ int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes,
  * length-bit and CRLF conditions are the caller's.  4 + len table steps. */
 uint64_t crc32c_locate_bit(uint32_t crc_computed, uint32_t crc_stored, uint64_t len);
 
+/* Restore one damaged byte from the stored CRC.  crc32c_repair_items and every
+ * flow built on it handle exactly one inverted bit; an image with two or more
+ * bits inverted inside ONE byte (a failed x8 DRAM device, a stuck lane, a torn
+ * byte) is dropped by all of them.  This call finds that byte and its XOR mask
+ * by the same search and puts the byte back.
+ *
+ * The rule, per image at o = item_offsets[i], in crc32c_repair_items' terms
+ * (sanity as crc32c_verify_items judges it, nt, L = nt - 32, c, e, S = c ^ e):
+ *   not sane, or L > max_span   ok = 0, byte = CRC32C_NO_BIT, mask = 0, nothing
+ *                               written.  max_span == 0 means
+ *                               CRC32C_REPAIR_BYTES_SPAN_DEFAULT; max_span >
+ *                               CRC32C_REPAIR_BYTES_SPAN_MAX: CRC32C_EINVAL.
+ *   S == 0                      ok = 1, byte = CRC32C_NO_BIT, mask = 0.
+ *   otherwise                   a pair (p, m) is located when p is an image
+ *     byte in [28, nt), m is in 1..255 and the image with byte p XORed by m has
+ *     a stored CRC equal to its computed one.  At most one pair exists (below).
+ *     A located pair is accepted when (1) m inverts no length-determining bit
+ *     -- p is not 32..35 or 41, not 38 with m & 0x02, not 39 with m & 0x01:
+ *     crc32c_repair_items' condition applied to each inverted bit -- and (2)
+ *     with the byte corrected nbytes >= 2 and the image's last two bytes are
+ *     "\r\n".
+ *     accepted                  ok = CRC32C_ITEM_REPAIRED, byte = p, mask = m
+ *                               (LSB = bit 0 of the byte); without
+ *                               CRC32C_LOCATE_ONLY that one byte of the buffer
+ *                               is XORed with m, so the image then passes
+ *                               crc32c_verify_items.
+ *     not located / accepted    ok = 0, byte = CRC32C_NO_BIT, mask = 0, nothing
+ *                               written.
+ * out->nrepaired counts ok == CRC32C_ITEM_REPAIRED and out->nbad counts ok == 0.
+ *
+ * What the rule guarantees.  In the syndrome form of crc32c_repair_items, V_j =
+ * S x^(-8 j) is non-zero and confined to the register's top byte exactly when
+ * the error pattern lies in the codeword byte of step j (step j < 4: stored-CRC
+ * byte 3 - j; step j >= 4: span byte L + 3 - j), and V_j >> 24 is that byte's
+ * mask.  Two one-byte patterns B and B' that lie d bytes apart share a syndrome
+ * iff B = B' x^(8 d) mod P.  Over all 255 patterns the smallest such d is
+ * 190 235 (0xdf against 0x4c; tests/integration/repair_bytes_check.cpp
+ * recomputes it).  So in a codeword of 4 + L <= 190 235 bytes -- L <=
+ * CRC32C_REPAIR_BYTES_SPAN_MAX -- damage confined to one byte is always
+ * located, at its own byte with its own mask and nowhere else, and accepted
+ * unless it inverts a length bit.  The single-bit masks are among the 255:
+ * within that bound the call finds everything crc32c_repair_items finds, at
+ * the same bit.
+ *
+ * The evidence is weaker, and that is the price.
+ *   - A syndrome that is as good as random passes for a one-byte error with
+ *     probability 255 (4 + L) / 2^32: 2^-12 for a 4 KiB image where the one-bit
+ *     rule has 2^-17, 2^-8 at the default max_span of 64 KiB -- 32 times the
+ *     one-bit rule's odds at equal length (255 patterns a byte against 8).
+ *   - The even-weight guarantee is gone.  Two inverted bits in DIFFERENT bytes,
+ *     which crc32c_repair_items never takes for a repair, are taken for a
+ *     one-byte error with that same probability.
+ * An image repaired by this call is the weakest evidence any call here gives:
+ * a separate, explicit call, not a mode of anything.  Run it after
+ * crc32c_repair_items on what is still 0, or instead of it where those odds
+ * are acceptable.  Damage spread over two bytes is
+ * not located; crc32c_scrub_pages does not use this call.
+ *
+ * Everything else is crc32c_repair_items': the work bound (the spans of the
+ * images with S != 0 and L <= max_span add up to more than base_bytes:
+ * CRC32C_EWORK, nothing written into the buffer, both counts 0); with
+ * CRC32C_DEVICE base, item_offsets and the three arrays are device memory and
+ * the call runs on opts->stream, the two counts are host words, read back, so
+ * CRC32C_ASYNC has no effect; without it the buffer is staged, the kernels run
+ * with the write off and the host applies the masks to the caller's buffer.
+ * CRC32C_EINVAL: NULL base, item_offsets, out, or any of the three arrays.
+ * n == 0: CRC32C_OK with zero counts.  No device: CRC32C_ENODEV, and neither
+ * `out` nor any array is written.  The read and write bounds are the same.
+ * After the call crc32c_last_kernel_ms() is the time of the search kernel alone
+ * (0 when no image had S != 0).  Scratch (grow-only): crc32c_repair_items', and
+ * a host call 2 B per image more. */
+#define CRC32C_REPAIR_BYTES_SPAN_MAX 190231u      /* 4 + L <= 190235: the located byte is unique */
+#define CRC32C_REPAIR_BYTES_SPAN_DEFAULT 0x10000u /* 255 (4 + L) / 2^32 = 2^-8, crc32c_repair_items' odds at its default */
+
+typedef struct crc32c_bytes_opts { /* NULL: all zero */
+    uint32_t mode;     /* CRC32C_DEVICE | CRC32C_CFLAGS64 | CRC32C_LOCATE_ONLY; others ignored */
+    uint32_t max_span; /* 0: the default; above CRC32C_REPAIR_BYTES_SPAN_MAX: CRC32C_EINVAL */
+    void *stream;
+} crc32c_bytes_opts;
+
+typedef struct crc32c_bytes_out {
+    /* in: n entries each (device memory with CRC32C_DEVICE) */
+    uint8_t *ok;
+    uint64_t *byte; /* image byte index, CRC32C_NO_BIT when none */
+    uint8_t *mask;  /* XOR mask of that byte, LSB = bit 0; 0 when none */
+    /* out: always filled, host words */
+    uint64_t nrepaired, nbad;
+} crc32c_bytes_out;
+
+int crc32c_repair_bytes(void *base, uint64_t base_bytes, uint64_t region_bytes,
+                        const uint64_t *item_offsets, uint64_t n,
+                        const crc32c_bytes_opts *opts, crc32c_bytes_out *out);
+
+/* The same search for one span on the host, no GPU.  Returns the codeword byte
+ * p -- p < 4: stored-CRC byte p, p >= 4: span byte p - 4; image byte 28 + p --
+ * with its XOR mask in *mask (optional), or CRC32C_NO_BIT with *mask = 0 when
+ * the two CRCs are equal, when no byte of a len-byte span explains them, or
+ * when len > CRC32C_REPAIR_BYTES_SPAN_MAX.  The length-bit and CRLF conditions
+ * are the caller's.  4 + len table steps. */
+uint64_t crc32c_locate_byte(uint32_t crc_computed, uint32_t crc_stored, uint64_t len, uint8_t *mask);
+
 /* Undo a flipped length bit in an item header.  crc32c_repair_items leaves the
  * 42 header bits that decide ITEM_ntotal alone: with one of them inverted the
  * image's span is no longer the one its CRC was made over.  That image is also
@@ -879,7 +984,7 @@ const char *crc32c_strerror(int err);
 /* Duration of this thread's last synchronous device batch (milliseconds,
  * hipEvent-measured on its stream); -1 before the first one.  After
  * crc32c_salvage_pages, crc32c_recover_pages and crc32c_triage_pages: the scan's
- * counting pass over the eligible bytes.  After crc32c_repair_items: the search kernel.  After
+ * counting pass over the eligible bytes.  After crc32c_repair_items and crc32c_repair_bytes: the search kernel.  After
  * crc32c_repair_headers: the variants' counting pass.  After
  * crc32c_scrub_pages: its last triage's counting pass. */
 float crc32c_last_kernel_ms(void);

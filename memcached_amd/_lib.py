@@ -38,6 +38,8 @@ CRC32C_ITEM_SUSPECT = 6  # kind[] of crc32c_triage_pages: an unreached candidate
 CRC32C_NO_BIT = 2**64 - 1  # bit[] of crc32c_repair_items / crc32c_locate_bit: no position
 CRC32C_REPAIR_SPAN_DEFAULT = 0x200000  # crc32c_repair_items' max_span when 0 is passed
 CRC32C_REPAIR_SPAN_MAX = 0x0FFFFFC0  # the longest span whose located position is unique
+CRC32C_REPAIR_BYTES_SPAN_MAX = 190231  # crc32c_repair_bytes: the longest span whose located byte is unique
+CRC32C_REPAIR_BYTES_SPAN_DEFAULT = 0x10000  # its max_span when 0 is passed
 CRC32C_HEADER_BITS = 42  # crc32c_repair_headers: the header bits that decide ITEM_ntotal, one variant each
 CRC32C_HEADER_WORK_MAX = 8  # its work bound: the candidate variants' spans per byte of the buffer
 CRC32C_SCRUB_ROUNDS_DEFAULT = 64  # crc32c_scrub_pages' max_rounds when 0 is passed
@@ -56,7 +58,8 @@ EXPORTED = (
     "crc32c_shard_cuts", "crc32c_queue_stats", "crc32c_host_register", "crc32c_host_unregister",
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
     "crc32c_set_k1_tail_min", "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit",
-    "crc32c_repair_headers", "crc32c_triage_pages", "crc32c_scrub_pages",
+    "crc32c_repair_headers", "crc32c_triage_pages", "crc32c_scrub_pages", "crc32c_repair_bytes",
+    "crc32c_locate_byte",
 )
 
 
@@ -116,6 +119,26 @@ class ScrubOut(ctypes.Structure):
     ]
 
 
+class BytesOpts(ctypes.Structure):
+    """crc32c_bytes_opts"""
+    _fields_ = [
+        ("mode", ctypes.c_uint32),
+        ("max_span", ctypes.c_uint32),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
+class BytesOut(ctypes.Structure):
+    """crc32c_bytes_out: the caller's three arrays, then the counts the call fills"""
+    _fields_ = [
+        ("ok", ctypes.c_void_p),
+        ("byte", ctypes.c_void_p),
+        ("mask", ctypes.c_void_p),
+        ("nrepaired", ctypes.c_uint64),
+        ("nbad", ctypes.c_uint64),
+    ]
+
+
 _INT, _UINT, _U32, _U64 = ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, ctypes.c_uint64
 _SIZE, _PTR, _SPANS, _U64P = ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(Spans), ctypes.POINTER(ctypes.c_uint64)
 _SCALAR = (_U32, [_U32, _PTR, _SIZE])  # crc_func of include/crc32c.h
@@ -146,6 +169,8 @@ PROTOTYPES = {
     "crc32c_locate_bit": (_U64, [_U32, _U32, _U64]),
     "crc32c_repair_headers": (_INT, [_PTR, _U64, _U64, _PTR, _U64, _PTR, _PTR, _PTR, _U64P, _U64P, _UINT, _PTR]),
     "crc32c_scrub_pages": (_INT, [_PTR, _U64, _U64, ctypes.POINTER(ScrubOpts), ctypes.POINTER(ScrubOut)]),
+    "crc32c_repair_bytes": (_INT, [_PTR, _U64, _U64, _PTR, _U64, ctypes.POINTER(BytesOpts), ctypes.POINTER(BytesOut)]),
+    "crc32c_locate_byte": (_U64, [_U32, _U32, _U64, ctypes.POINTER(ctypes.c_uint8)]),
     "crc32c_batch_chains": (_INT, [_SPANS, _PTR, _U64, _PTR, _UINT, _PTR]),
     "crc32c_host_alloc": (_PTR, [_SIZE]),
     "crc32c_host_free": (None, [_PTR]),
@@ -163,7 +188,7 @@ PROTOTYPES = {
 # what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
 NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min",
          "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit", "crc32c_repair_headers",
-         "crc32c_triage_pages", "crc32c_scrub_pages")
+         "crc32c_triage_pages", "crc32c_scrub_pages", "crc32c_repair_bytes", "crc32c_locate_byte")
 
 
 def _load():

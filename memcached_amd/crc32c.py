@@ -16,6 +16,8 @@ include/crc32c_batch.h and run the gfx950 kernels:
 * ``triage_pages`` recover_pages plus the unreached candidates whose stored CRC fails (kind 6), for repair_items
 * ``repair_items`` single-bit damage of item images located by the stored CRC and flipped back
   (``locate_bit``: the same search for one span on the host)
+* ``repair_bytes`` damage confined to one byte (any of its 255 masks) located by the stored CRC and put back, on 32
+  times weaker evidence than repair_items' (``locate_byte``: the same search for one span on the host)
 * ``repair_headers`` a flipped length bit of an item header found among the 42 headers one bit away
 * ``scrub_pages`` triage_pages, repair_headers and repair_items round by round in one call: the final list and a flip log
 * ``batch_chains`` chained CRCs of chunked items over iov lists (storage.c:163-170)
@@ -37,8 +39,8 @@ from . import _lib
 from ._lib import (CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, CRC32C_SCRUB_GAPS, Crc32cError, check,
                    lib)
 
-# (recover_pages, triage_pages, repair_items, locate_bit, repair_headers and scrub_pages are public as well; tests/test_python_face.py pins this list as it
-# stood before them)
+# (recover_pages, triage_pages, repair_items, locate_bit, repair_headers, scrub_pages, repair_bytes and locate_byte are
+# public as well; tests/test_python_face.py pins this list as it stood before them)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
            "batch_multi",
@@ -529,6 +531,49 @@ def repair_items(buf, item_offsets, region_bytes=0, max_span=0, locate_only=Fals
                                   ctypes.byref(nrepaired), ctypes.byref(nbad), flags, side.stream),
           "crc32c_repair_items")
     return ok, bit, {"nrepaired": int(nrepaired.value), "nbad": int(nbad.value)}
+
+
+def repair_bytes(buf, item_offsets, region_bytes=0, max_span=0, locate_only=False, stream=None, cflags64=False):
+    """Restore one damaged byte of item images from their stored CRC
+    (crc32c_repair_bytes): for every image whose stored CRC does not match,
+    the one byte of its stored CRC or span and the XOR mask (any of the 255)
+    that explain the mismatch are looked for; when they exist, the mask
+    inverts no length-determining header bit and the corrected value ends in
+    CRLF, the byte is put back in ``buf``.
+
+    Returns (ok, byte, mask, {"nrepaired", "nbad"}) for numpy and torch
+    buffers: ok[i] is 1 for an intact image, CRC32C_ITEM_REPAIRED (5) for a
+    repaired one with byte[i] the image's byte index and mask[i] what it was
+    XORed with, else 0 with byte[i] = CRC32C_NO_BIT and mask[i] = 0 (not sane,
+    longer than ``max_span`` -- 0: 64 KiB, at most
+    CRC32C_REPAIR_BYTES_SPAN_MAX -- or not explained by one byte).  Everything
+    repair_items finds this call finds too, but on 32 times weaker evidence: a
+    damaged image of another kind (two bits in different bytes included)
+    passes for a one-byte error with probability 255 (4 + L) / 2^32.
+    ``locate_only``, ``region_bytes``, ``cflags64`` and CRC32C_EWORK as for
+    repair_items."""
+    side = _side(buf, stream)
+    buf, nbytes = side.buffer(buf, inplace=None if locate_only else
+                              "repair_bytes needs {} (repaired in place) unless locate_only is set")
+    offs = side.desc(item_offsets, "item_offsets", _U64)
+    n = _count(offs)
+    ok, byte, mask = side.empty(max(n, 1), _U8), side.empty(max(n, 1), _U64), side.empty(max(n, 1), _U8)
+    opts = _lib.BytesOpts(side.flag | _flags(cflags64) | (_lib.CRC32C_LOCATE_ONLY if locate_only else 0), max_span,
+                          side.stream)
+    out = _lib.BytesOut(_ptr(ok), _ptr(byte), _ptr(mask), 0, 0)
+    check(lib.crc32c_repair_bytes(_ptr(buf), nbytes, region_bytes, _ptr(offs), n, ctypes.byref(opts),
+                                  ctypes.byref(out)), "crc32c_repair_bytes")
+    return ok[:n], byte[:n], mask[:n], {"nrepaired": int(out.nrepaired), "nbad": int(out.nbad)}
+
+
+def locate_byte(crc_computed: int, crc_stored: int, length: int):
+    """crc32c_locate_byte, on the host: (p, mask) -- the one byte of a
+    ``length``-byte span or of its stored CRC (p < 4: stored-CRC byte p; else
+    span byte p - 4) and the XOR mask that turn ``crc_stored`` into a match
+    for ``crc_computed`` -- or None."""
+    mask = ctypes.c_uint8(0)
+    p = int(lib.crc32c_locate_byte(crc_computed & 0xFFFFFFFF, crc_stored & 0xFFFFFFFF, length, ctypes.byref(mask)))
+    return None if p == _lib.CRC32C_NO_BIT else (p, int(mask.value))
 
 
 def repair_headers(buf, item_offsets, region_bytes=0, locate_only=False, stream=None, cflags64=False):

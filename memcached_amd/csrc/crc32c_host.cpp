@@ -231,3 +231,22 @@ extern "C" uint64_t crc32c_locate_bit(uint32_t crc_computed, uint32_t crc_stored
     }
     return CRC32C_NO_BIT;
 }
+
+// crc32c_locate_byte (crc32c_batch.h): the search of crc32c_repair_bytes for one
+// span, with the same per-call table.
+extern "C" uint64_t crc32c_locate_byte(uint32_t crc_computed, uint32_t crc_stored, uint64_t len, uint8_t *mask) {
+    uint32_t v = crc_computed ^ crc_stored;
+    if (mask) *mask = 0;
+    if (v == 0 || len > mcrc::kRepairBytesSpanMax) return CRC32C_NO_BIT;
+    uint32_t inv8[256];
+    for (uint32_t b = 0; b < 256; ++b) inv8[b] = mcrc::repair_unstep8(b << 24);
+    const uint64_t steps = mcrc::repair_steps(len);
+    for (uint64_t j = 0; j < steps; ++j) {
+        if (mcrc::repair_byte_hit(v)) {
+            if (mask) *mask = (uint8_t)mcrc::repair_byte_mask(v);
+            return mcrc::repair_byte_of_step(j, len);
+        }
+        v = (v << 8) ^ inv8[v >> 24];
+    }
+    return CRC32C_NO_BIT;
+}

@@ -45,3 +45,4 @@
 #include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply
 #include "k_triage.h"  // crc32c_triage_pages: k_triage_pick, k_triage_merge
 #include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_log
+#include "k_repair_bytes.h"  // crc32c_repair_bytes: k_repair_bytes_search, k_repair_bytes_apply

@@ -363,6 +363,11 @@ int crc32c_repair_items(void *base, uint64_t base_bytes, uint64_t region_bytes, 
                         stream);
 }
 
+int crc32c_repair_bytes(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets,
+                        uint64_t n, const crc32c_bytes_opts *opts, crc32c_bytes_out *out) {
+    return repair_bytes(base, base_bytes, region_bytes, item_offsets, n, opts, out);
+}
+
 int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes, const uint64_t *item_offsets,
                           uint64_t n, uint8_t *ok, uint64_t *bit, uint32_t *lens, uint64_t *nrepaired, uint64_t *nbad,
                           unsigned flags, void *stream) {

@@ -2,8 +2,10 @@
 // positions of an image's stored CRC and span, the exponent t each one has in
 // the syndrome, the one-bit step and its inverse, the byte step the search
 // takes, the chunks it is cut into and the header bits that decide an image's
-// length.  Plain C++ over k_consts.h (k_repair.h, shim_repair.h and
-// crc32c_locate_bit use it; tests/integration/repair_geom_check.cpp runs it on
+// length, and at the end crc32c_repair_bytes' byte hit test and maps.  Plain
+// C++ over k_consts.h (k_repair.h, k_repair_bytes.h, shim_repair.h,
+// crc32c_locate_bit and crc32c_locate_byte use it;
+// tests/integration/repair_geom_check.cpp and repair_bytes_check.cpp run it on
 // the CPU).
 //
 // The rule (include/crc32c_batch.h).  A register holds a polynomial mod P
@@ -85,6 +87,29 @@ MCRC_HD uint64_t repair_chunk_pow(uint64_t j0) { return j0 ? kRepairOrder - j0 :
 MCRC_HD bool repair_length_bit(uint64_t k) {
     const uint64_t byte = k / 8, b = k % 8;
     return (byte >= 32 && byte <= 35) || byte == 41 || (byte == 38 && b == 1) || (byte == 39 && b == 0);
+}
+
+// crc32c_repair_bytes: the same search with another hit test.  V_j = S x^(-8 j)
+// is non-zero and confined to the register's top byte exactly when the error
+// pattern V_j lies in the codeword byte that step j covers, whatever its
+// weight; bit 31 - r of V_j is that byte's bit 7 - r (repair_q_of_t of t =
+// 8 j + r), so V_j >> 24 is the byte's XOR mask as it stands.  Two one-byte
+// patterns d bytes apart share a syndrome iff B = B' x^(8 d) mod P; the smallest
+// such d over all 255 patterns is 190 235 (0xdf against 0x4c;
+// tests/integration/repair_bytes_check.cpp recomputes it), so a codeword of
+// 4 + L <= 190 235 bytes has its damaged byte located at one place only.
+constexpr uint32_t kRepairBytesSpanMax = 190231u;       // CRC32C_REPAIR_BYTES_SPAN_MAX: 4 + L <= 190 235
+constexpr uint32_t kRepairBytesSpanDefault = 0x10000u;  // CRC32C_REPAIR_BYTES_SPAN_DEFAULT
+MCRC_HD bool repair_byte_hit(uint32_t v) { return v != 0u && !(v & 0x00ffffffu); }
+MCRC_HD uint32_t repair_byte_mask(uint32_t v) { return v >> 24; }  // (v: a byte hit)
+// Codeword bytes: p < 4 is stored-CRC byte p, p >= 4 span byte p - 4 (image byte
+// 28 + p).  Step j < 4 covers stored-CRC byte 3 - j, step j >= 4 span byte
+// L + 3 - j; the map is its own inverse.
+MCRC_HD uint64_t repair_byte_of_step(uint64_t j, uint64_t len) { return j < 4 ? 3 - j : len + 7 - j; }
+MCRC_HD uint64_t repair_step_of_byte(uint64_t p, uint64_t len) { return p < 4 ? 3 - p : len + 7 - p; }
+// repair_length_bit for each bit that mask m inverts in image byte `byte`.
+MCRC_HD bool repair_length_mask(uint64_t byte, uint32_t m) {
+    return (byte >= 32 && byte <= 35) || byte == 41 || (byte == 38 && (m & 0x02u)) || (byte == 39 && (m & 0x01u));
 }
 
 }  // namespace mcrc

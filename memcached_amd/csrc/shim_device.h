@@ -150,6 +150,9 @@ struct Device {
     DevBuf<uint8_t> rp_ok;
     DevBuf<uint64_t> rp_bit;
     PinBuf<uint64_t> rp_hbit;
+    // crc32c_repair_bytes: a host call's masks (the rest is crc32c_repair_items')
+    DevBuf<uint8_t> rp_mask;
+    PinBuf<uint8_t> rp_hmask;
     // crc32c_repair_headers: per header its candidates' count and scan; per
     // candidate its span (offset, length), record and CRC; the counters and
     // their pinned twin; a host call's verdicts, positions and lengths
