@@ -15,10 +15,9 @@
  * check, runs over both lists.  Only the images whose own header was damaged
  * stay lost.
  *
- * The run: fill a page of 8 wbufs with stamped images, keep a key -> offset
- * table as the hash table, mark two fifths of the items live, flip one header
- * bit (nkey, nbytes or it_flags, in turn) of every 37th live image "on
- * flash", then run the read-back either way.
+ * The run: readback_page.h's page with the header damage alone
+ * (DAMAGE_HEADERS): one header bit (nkey, nbytes or it_flags, in turn) of
+ * every 37th live image flipped "on flash", then the read-back either way.
  *
  * Usage: salvage_sim [--gpu] [--walk]
  * Prints live=<l> reached=<r> salvaged=<s> lost=<x> damaged=<d>: reached = live
@@ -26,85 +25,7 @@
  * the salvage added, lost = live - reached - salvaged.  Exit status 0 = the run
  * itself worked; the caller judges the counts.
  */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "crc32c.h"
-#include "crc32c_batch.h"
-
-#define WBUF (1u << 20)
-#define NWBUF 8u
-#define PAGE (NWBUF * WBUF)
-#define MAX_ITEMS 8000u
-#define ITEM_CAS 2u
-#define MAX_VALUE 3000u
-#define MAX_IMG (48 + 16 + 8 + MAX_VALUE + 2)
-#define GONE UINT64_MAX
-
-static uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-
-static uint64_t ntotal_of(const uint8_t *p) {
-    uint16_t flags;
-    memcpy(&flags, p + 38, 2);
-    return 48ull + p[41] + 1 + rd32(p + 32) + ((flags & 256u) ? 4 : 0) + ((flags & ITEM_CAS) ? 8 : 0);
-}
-
-static uint64_t mix(uint64_t *s) {
-    uint64_t z = (*s += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-/* an item image as storage_write leaves it, CRC stored (storage.c:567) */
-static uint32_t make_image(uint8_t *img, uint32_t id, uint64_t *rng) {
-    char key[16];
-    const int nkey = snprintf(key, sizeof key, "key%07u", id);
-    const uint32_t vlen = (uint32_t)(mix(rng) % MAX_VALUE), nbytes = vlen + 2;
-    const uint32_t nt = 48 + (uint32_t)nkey + 1 + nbytes + 8;
-    const uint16_t refc = 1, flags = ITEM_CAS | 1u /* ITEM_LINKED */;
-    const uint64_t cas = id + 1;
-    memset(img, 0, 48);
-    memcpy(img + 32, &nbytes, 4);
-    memcpy(img + 36, &refc, 2);
-    memcpy(img + 38, &flags, 2);
-    img[40] = 17;
-    img[41] = (uint8_t)nkey;
-    memcpy(img + 48, &cas, 8);
-    memcpy(img + 56, key, (size_t)nkey + 1);
-    uint8_t *v = img + 56 + nkey + 1;
-    for (uint32_t i = 0; i < vlen; ++i) v[i] = (uint8_t)mix(rng);
-    v[vlen] = '\r';
-    v[vlen + 1] = '\n';
-    const uint32_t crc = crc32c(0, img + 32, nt - 32);
-    memcpy(img + 28, &crc, 4);
-    return nt;
-}
-
-static uint64_t where[MAX_ITEMS]; /* the hash table: page offset of each live item's image, or GONE */
-static uint8_t damaged[MAX_ITEMS], rescued[MAX_ITEMS];
-static uint32_t nitems;
-
-/* storage.c:964-975: the image's key, looked up, must be linked to exactly
- * this offset (`room` bytes of the wbuf are left behind it) */
-static int rescue(const uint8_t *page, uint64_t off, uint64_t room) {
-    const uint8_t *im = page + off;
-    uint16_t flags;
-    memcpy(&flags, im + 38, 2);
-    const uint32_t nkey = im[41], koff = 48 + ((flags & ITEM_CAS) ? 8 : 0);
-    char key[16];
-    if (nkey != 10 || koff + nkey > room) return 0;
-    memcpy(key, im + koff, nkey);
-    key[nkey] = 0;
-    if (strncmp(key, "key", 3) != 0) return 0;
-    char *end = NULL;
-    const unsigned long id = strtoul(key + 3, &end, 10);
-    if (*end || id >= nitems || where[id] != off || rescued[id]) return 0;
-    rescued[id] = 1;
-    return 1;
-}
+#include "readback_page.h"
 
 int main(int argc, char **argv) {
     int gpu = 0, walk_only = 0;
@@ -115,86 +36,52 @@ int main(int argc, char **argv) {
     crc32c_init();
     if (!gpu) {
         uint8_t buf[64] = {0};
-        uint64_t offs[1] = {9}, nfound = 9;
-        const int rc = crc32c_salvage_pages(buf, sizeof buf, 64, NULL, NULL, 0, offs, 1, &nfound, NULL, NULL, 0, NULL);
+        uint64_t o1[1] = {9}, nfound = 9;
+        const int rc = crc32c_salvage_pages(buf, sizeof buf, 64, NULL, NULL, 0, o1, 1, &nfound, NULL, NULL, 0, NULL);
         printf("salvage_sim: no GPU, salvage reports %s\n", crc32c_strerror(rc));
-        return rc == CRC32C_ENODEV && offs[0] == 9 && nfound == 9 ? 0 : 1;
+        return rc == CRC32C_ENODEV && o1[0] == 9 && nfound == 9 ? 0 : 1;
     }
-    uint8_t *page = calloc(PAGE, 1);
-    static uint8_t img[MAX_IMG];
-    if (!page) return 1;
-    int failures = 0;
-    uint64_t rng = 41;
-
-    /* fill the page through wbufs: an image never crosses one, tails stay zero */
-    uint64_t used = 0;
-    for (;; ++nitems) {
-        const uint32_t nt = make_image(img, nitems, &rng);
-        if (used % WBUF + nt > WBUF) used = (used / WBUF + 1) * WBUF;
-        if (used >= PAGE) break;
-        if (nitems >= MAX_ITEMS) {
-            fprintf(stderr, "item table too small\n");
-            return 1;
-        }
-        memcpy(page + used, img, nt);
-        where[nitems] = used;
-        used += nt;
-    }
-
-    /* the live set, and the damage "on flash": one header bit of every 37th live image */
-    uint64_t live = 0, ndamaged = 0;
-    for (uint32_t id = 0; id < nitems; ++id) {
-        if (mix(&rng) % 5 >= 2) {
-            where[id] = GONE;
-            continue;
-        }
-        if (live++ % 37 == 11) {
-            uint8_t *im = page + where[id];
-            switch (ndamaged % 3) {
-                case 0: im[41] = 0; break;                                   /* nkey: ends the walk */
-                case 1: im[32 + mix(&rng) % 2] ^= (uint8_t)(1u << (mix(&rng) % 8)); break; /* nbytes */
-                default: im[38] ^= ITEM_CAS; break;                          /* it_flags */
-            }
-            damaged[id] = 1;
-            ++ndamaged;
-        }
-    }
+    uint8_t *page = malloc(PAGE);
+    struct page_counts c;
+    if (!page || page_build(page, NULL, DAMAGE_HEADERS, &c) != 0) return 1;
 
     uint64_t reached = 0, salvaged = 0;
-    if (walk_only) { /* storage.c:950-1072 as it is */
+    if (walk_only) { /* storage.c:950-1072 as it is: no CRC is checked and the rescue check may read up to the wbuf's
+                      * end, which readback_page.h's reference_walk does otherwise */
         for (uint32_t w = 0; w < NWBUF; ++w) {
             uint64_t off = 0;
             while (off + 48 <= WBUF && page[w * (uint64_t)WBUF + off + 41] != 0) {
-                const uint64_t at = w * (uint64_t)WBUF + off;
-                reached += rescue(page, at, WBUF - off);
-                off += ntotal_of(page + at);
+                const uint64_t o = w * (uint64_t)WBUF + off;
+                reached += rescue(page, o, WBUF - off, NULL);
+                off += ntotal_of(page + o);
             }
         }
-    } else {
-        const uint64_t cap = PAGE / 50 + NWBUF;
-        uint64_t *offs = malloc(cap * 8), *found = malloc(cap * 8);
-        uint8_t *ok = malloc(cap);
-        uint64_t n = 0, nbad = 0, nfound = 0, scanned = 0, ncand = 0;
-        if (!offs || !found || !ok) return 1;
-        int rc = crc32c_verify_pages(page, PAGE, WBUF, offs, ok, cap, &n, &nbad, 0, NULL);
-        if (rc != CRC32C_OK || n > cap) {
+    } else { /* (the walk's list has ok[] for kind[] and no lens[]: it is not readback_page.h's list) */
+        const uint64_t room = PAGE / 50 + NWBUF;
+        uint64_t *walked = malloc(room * 8), *found = malloc(room * 8);
+        uint8_t *ok = malloc(room);
+        uint64_t nwalked = 0, nbad = 0, nfound = 0, scanned = 0, ncand = 0;
+        if (!walked || !found || !ok) return 1;
+        int rc = crc32c_verify_pages(page, PAGE, WBUF, walked, ok, room, &nwalked, &nbad, 0, NULL);
+        if (rc != CRC32C_OK || nwalked > room) {
             fprintf(stderr, "crc32c_verify_pages: %s\n", crc32c_strerror(rc));
             ++failures;
-            n = 0;
+            nwalked = 0;
         }
-        for (uint64_t k = 0; k < n; ++k)
-            if (ok[k]) reached += rescue(page, offs[k], WBUF - offs[k] % WBUF);
-        rc = crc32c_salvage_pages(page, PAGE, WBUF, offs, ok, n, found, cap, &nfound, &scanned, &ncand, 0, NULL);
-        if (rc != CRC32C_OK || nfound > cap) {
+        for (uint64_t k = 0; k < nwalked; ++k)
+            if (ok[k]) reached += rescue(page, walked[k], WBUF - walked[k] % WBUF, NULL);
+        rc = crc32c_salvage_pages(page, PAGE, WBUF, walked, ok, nwalked, found, room, &nfound, &scanned, &ncand, 0,
+                                  NULL);
+        if (rc != CRC32C_OK || nfound > room) {
             fprintf(stderr, "crc32c_salvage_pages: %s\n", crc32c_strerror(rc));
             ++failures;
             nfound = 0;
         }
-        for (uint64_t k = 0; k < nfound; ++k) salvaged += rescue(page, found[k], WBUF - found[k] % WBUF);
+        for (uint64_t k = 0; k < nfound; ++k) salvaged += rescue(page, found[k], WBUF - found[k] % WBUF, NULL);
         printf("salvage_sim: walk items %llu bad %llu, salvage found %llu of %llu candidates in %llu offsets\n",
-               (unsigned long long)n, (unsigned long long)nbad, (unsigned long long)nfound, (unsigned long long)ncand,
-               (unsigned long long)scanned);
-        free(offs);
+               (unsigned long long)nwalked, (unsigned long long)nbad, (unsigned long long)nfound,
+               (unsigned long long)ncand, (unsigned long long)scanned);
+        free(walked);
         free(found);
         free(ok);
     }
@@ -210,9 +97,9 @@ int main(int argc, char **argv) {
     if (good != reached + salvaged) ++failures;
     printf("salvage_sim: %s, %u items, failures %d\n", walk_only ? "walk" : "verify_pages + salvage_pages", nitems,
            failures);
-    printf("live=%llu reached=%llu salvaged=%llu lost=%llu damaged=%llu\n", (unsigned long long)live,
-           (unsigned long long)reached, (unsigned long long)salvaged, (unsigned long long)(live - reached - salvaged),
-           (unsigned long long)ndamaged);
+    printf("live=%llu reached=%llu salvaged=%llu lost=%llu damaged=%llu\n", (unsigned long long)c.live,
+           (unsigned long long)reached, (unsigned long long)salvaged, (unsigned long long)(c.live - reached - salvaged),
+           (unsigned long long)c.ndamaged);
     free(page);
     return failures == 0 ? 0 : 1;
 }

@@ -1,5 +1,5 @@
 /* triage_sim.c -- header_sim.c's read-back of a page with damaged headers and
- * damaged data (the same generator, seeds and damage), played twice over the
+ * damaged data (readback_page.h's page, DAMAGE_LENGTHS), played twice over the
  * same damaged bytes:
  *   the old flow  header_sim.c's: crc32c_recover_pages, rounds of
  *                 crc32c_repair_headers, crc32c_repair_items over the entries
@@ -29,117 +29,11 @@
  * (u = x + y + z).  Exit status 0 = the run itself worked; the caller judges
  * the counts.
  */
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "readback_page.h"
 
-#include "crc32c.h"
-#include "crc32c_batch.h"
-
-#define WBUF (1u << 20)
-#define NWBUF 8u
-#define PAGE (NWBUF * WBUF)
-#define MAX_ITEMS 8000u
-#define ITEM_CAS 2u
-#define MAX_VALUE 3000u
-#define MAX_IMG (48 + 16 + 8 + MAX_VALUE + 2)
-#define GONE UINT64_MAX
-#define MAX_ROUNDS 64
-
-static uint64_t mix(uint64_t *s) {
-    uint64_t z = (*s += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-/* an item image as storage_write leaves it, CRC stored (storage.c:567) */
-static uint32_t make_image(uint8_t *img, uint32_t id, uint64_t *rng) {
-    char key[16];
-    const int nkey = snprintf(key, sizeof key, "key%07u", id);
-    const uint32_t vlen = (uint32_t)(mix(rng) % MAX_VALUE), nbytes = vlen + 2;
-    const uint32_t nt = 48 + (uint32_t)nkey + 1 + nbytes + 8;
-    const uint16_t refc = 1, flags = ITEM_CAS | 1u /* ITEM_LINKED */;
-    const uint64_t cas = id + 1;
-    memset(img, 0, 48);
-    memcpy(img + 32, &nbytes, 4);
-    memcpy(img + 36, &refc, 2);
-    memcpy(img + 38, &flags, 2);
-    img[40] = 17;
-    img[41] = (uint8_t)nkey;
-    memcpy(img + 48, &cas, 8);
-    memcpy(img + 56, key, (size_t)nkey + 1);
-    uint8_t *v = img + 56 + nkey + 1;
-    for (uint32_t i = 0; i < vlen; ++i) v[i] = (uint8_t)mix(rng);
-    v[vlen] = '\r';
-    v[vlen + 1] = '\n';
-    const uint32_t crc = crc32c(0, img + 32, nt - 32);
-    memcpy(img + 28, &crc, 4);
-    return nt;
-}
-
-static uint64_t where[MAX_ITEMS]; /* the hash table: page offset of each live item's image, or GONE */
-static uint32_t size_of[MAX_ITEMS]; /* the ITEM_ntotal each image was written with */
-static uint64_t at[MAX_ITEMS];     /* where each image was written, live or not */
-static uint8_t damaged[MAX_ITEMS], rescued[MAX_ITEMS], dead[MAX_ITEMS]; /* dead: nkey zeroed */
-static uint32_t nitems;
-
-/* storage.c:964-975: the image's key, looked up, must be linked to exactly
- * this offset (`room`: the image's bytes) */
-static int rescue(const uint8_t *page, uint64_t off, uint64_t room) {
-    const uint8_t *im = page + off;
-    uint16_t flags;
-    memcpy(&flags, im + 38, 2);
-    const uint32_t nkey = im[41], koff = 48 + ((flags & ITEM_CAS) ? 8 : 0);
-    char key[16];
-    if (nkey != 10 || koff + nkey > room) return 0;
-    memcpy(key, im + koff, nkey);
-    key[nkey] = 0;
-    if (strncmp(key, "key", 3) != 0) return 0;
-    char *end = NULL;
-    const unsigned long id = strtoul(key + 3, &end, 10);
-    if (*end || id >= nitems || where[id] != off || rescued[id]) return 0;
-    rescued[id] = 1;
-    return 1;
-}
-
-/* the 42 length bits (crc32c_batch.h), by image bit index */
-static uint32_t length_bit_of(uint32_t v) { return v < 32 ? 256 + v : v < 40 ? 328 + (v - 32) : v == 40 ? 305 : 312; }
-static int length_bit(uint64_t k) {
-    const uint64_t by = k / 8, b = k % 8;
-    return (by >= 32 && by <= 35) || by == 41 || (by == 38 && b == 1) || (by == 39 && b == 0);
-}
-
-static uint64_t *offs, *todo, *bit;
-static uint32_t *lens, *hlens;
-static uint8_t *kind, *ok;
-static uint64_t cap, n;
-static int failures, triage;
-
-/* the page's list: crc32c_recover_pages (the old flow) or crc32c_triage_pages */
-static void recover(uint8_t *page) {
-    uint64_t nbad = 0, nsalvaged = 0, nsuspect = 0;
-    const int rc = triage ? crc32c_triage_pages(page, PAGE, WBUF, offs, lens, kind, cap, &n, &nbad, &nsalvaged, &nsuspect,
-                                                NULL, NULL, 0, NULL)
-                          : crc32c_recover_pages(page, PAGE, WBUF, offs, lens, kind, cap, &n, &nbad, &nsalvaged, NULL,
-                                                 NULL, 0, NULL);
-    if (rc != CRC32C_OK || n > cap) {
-        fprintf(stderr, "%s: %s\n", triage ? "crc32c_triage_pages" : "crc32c_recover_pages", crc32c_strerror(rc));
-        ++failures;
-        n = 0;
-    }
-}
-
-/* one read-back and rescue loop: the live items lost */
-static uint64_t lost_now(uint8_t *page, uint64_t live) {
-    memset(rescued, 0, sizeof rescued);
-    recover(page);
-    uint64_t got = 0;
-    for (uint64_t k = 0; k < n; ++k)
-        if (kind[k] != 0 && kind[k] != CRC32C_ITEM_SUSPECT) got += (uint64_t)rescue(page, offs[k], lens[k]);
-    return live - got;
-}
+static uint64_t *todo, *bit;
+static uint32_t *hlens;
+static uint8_t *ok;
 
 struct flow {
     uint64_t lost_recover, lost_headers, lost_items, headers_repaired, items_repaired, suspects, suspects_kept;
@@ -155,19 +49,7 @@ static struct flow play(uint8_t *page, uint64_t live) {
 
     /* stage 2: the headers, round by round (lost_now left the walk's lists behind) */
     for (; f.rounds < MAX_ROUNDS; ++f.rounds) {
-        uint64_t m = 0, k = 0;
-        for (uint64_t w = 0; w * WBUF < PAGE; ++w) { /* INTEGRATION.md 4f */
-            const uint64_t ps = w * WBUF, pe = ps + WBUF < PAGE ? ps + WBUF : PAGE;
-            uint64_t end = ps;
-            int last = -1;
-            for (; k < n && offs[k] < pe; ++k) {
-                if (kind[k] == CRC32C_ITEM_SALVAGED || kind[k] == CRC32C_ITEM_SUSPECT) continue;
-                if (kind[k] == 0) todo[m++] = offs[k];
-                last = kind[k];
-                end = offs[k] + lens[k];
-            }
-            if (last != 0 && end >= ps && end <= pe && pe - end >= 48) todo[m++] = end;
-        }
+        const uint64_t m = header_list(todo); /* INTEGRATION.md 4f */
         uint64_t nrep = 0, nleft = 0;
         const int rc = crc32c_repair_headers(page, PAGE, WBUF, todo, m, ok, bit, hlens, &nrep, &nleft, 0, NULL);
         if (rc != CRC32C_OK) {
@@ -184,19 +66,8 @@ static struct flow play(uint8_t *page, uint64_t live) {
     /* stage 3: the damaged sane entries of the last walk and, in one pass over the ascending list, the suspects
      * that end at or before the next proven entry (kind 1 or 4) and start at or behind the last suspect kept
      *  */
-    uint64_t m = 0, nleft = 0, j = 0, kept_end = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-        if (kind[k] == 0 && lens[k] != 0) todo[m++] = offs[k];
-        if (kind[k] != CRC32C_ITEM_SUSPECT) continue;
-        ++f.suspects;
-        if (j <= k) j = k + 1;
-        while (j < n && kind[j] != 1 && kind[j] != CRC32C_ITEM_SALVAGED) ++j;
-        const uint64_t next = j < n ? offs[j] : UINT64_MAX, end = offs[k] + lens[k];
-        if (end > next || offs[k] < kept_end) continue;
-        todo[m++] = offs[k];
-        kept_end = end;
-        ++f.suspects_kept;
-    }
+    uint64_t nleft = 0;
+    const uint64_t m = item_list(todo, &f.suspects, &f.suspects_kept);
     const int rc = crc32c_repair_items(page, PAGE, WBUF, todo, m, 0, ok, bit, &f.items_repaired, &nleft, 0, NULL);
     if (rc != CRC32C_OK) {
         fprintf(stderr, "crc32c_repair_items: %s\n", crc32c_strerror(rc));
@@ -222,80 +93,17 @@ int main(int argc, char **argv) {
         for (int i = 0; i < 6; ++i) same &= c[i] == 9;
         return rc == CRC32C_ENODEV && same ? 0 : 1;
     }
-    uint8_t *page = calloc(PAGE, 1), *pristine = malloc(PAGE), *old = malloc(PAGE);
-    static uint8_t img[MAX_IMG];
-    if (!page || !pristine || !old) return 1;
-    uint64_t rng = 41;
-
-    /* fill the page through wbufs: an image never crosses one, tails stay zero */
-    uint64_t used = 0;
-    for (;; ++nitems) {
-        const uint32_t nt = make_image(img, nitems, &rng);
-        if (used % WBUF + nt > WBUF) used = (used / WBUF + 1) * WBUF;
-        if (used >= PAGE) break;
-        if (nitems >= MAX_ITEMS) {
-            fprintf(stderr, "item table too small\n");
-            return 1;
-        }
-        memcpy(page + used, img, nt);
-        where[nitems] = at[nitems] = used;
-        size_of[nitems] = nt;
-        used += nt;
-    }
-    memcpy(pristine, page, PAGE);
-
-    /* the live set, and the damage "on flash": one header bit of every 37th live image (recover_sim.c's) */
-    uint64_t live = 0, ndamaged = 0;
-    for (uint32_t id = 0; id < nitems; ++id) {
-        if (mix(&rng) % 5 >= 2) {
-            where[id] = GONE;
-            continue;
-        }
-        if (live++ % 37 == 11) {
-            uint8_t *im = page + where[id];
-            switch (ndamaged % 3) {
-                case 0: im[41] = 0; dead[id] = 1; break;                     /* nkey: ends the walk */
-                case 1: im[32 + mix(&rng) % 2] ^= (uint8_t)(1u << (mix(&rng) % 8)); break; /* nbytes */
-                default: im[38] ^= ITEM_CAS; break;                          /* it_flags */
-            }
-            damaged[id] = 1;
-            ++ndamaged;
-        }
-    }
-    /* ... one of the 42 length bits of every 11th of the other live images; of the rest every 7th one bit of the
-     * stored CRC or the bytes it covers (no length bit), every fifth of those a second one */
-    uint64_t rng2 = 77, nth = 0, nlen = 0, ndata = 0;
-    for (uint32_t id = 0; id < nitems; ++id) {
-        if (where[id] == GONE || damaged[id]) continue;
-        uint8_t *im = page + where[id];
-        const uint64_t turn = nth++;
-        if (turn % 11 == 5) {
-            const uint32_t k = length_bit_of((uint32_t)(mix(&rng2) % CRC32C_HEADER_BITS));
-            im[k / 8] ^= (uint8_t)(1u << (k % 8));
-            damaged[id] = 3;
-            ++nlen;
-        } else if (turn % 7 == 3) {
-            const uint64_t nbits = 8ull * size_of[id] - 224;
-            uint64_t k1;
-            do k1 = 224 + mix(&rng2) % nbits; while (length_bit(k1));
-            im[k1 / 8] ^= (uint8_t)(1u << (k1 % 8));
-            if (ndata % 5 == 4) {
-                uint64_t k2;
-                do k2 = 224 + mix(&rng2) % nbits; while (length_bit(k2) || k2 == k1);
-                im[k2 / 8] ^= (uint8_t)(1u << (k2 % 8));
-            }
-            damaged[id] = 2;
-            ++ndata;
-        }
-    }
+    uint8_t *page = malloc(PAGE), *pristine = malloc(PAGE), *old = malloc(PAGE);
+    struct page_counts c;
+    if (!page || !pristine || !old || page_build(page, pristine, DAMAGE_LENGTHS, &c) != 0) return 1;
+    const uint64_t live = c.live;
     memcpy(old, page, PAGE);
 
     /* (suspects may overlap: their number is bounded by the candidates, not by the page's bytes over 50) */
-    cap = 4 * (PAGE / 50) + NWBUF;
-    offs = malloc(cap * 8), todo = malloc((cap + NWBUF) * 8), bit = malloc((cap + NWBUF) * 8);
-    lens = malloc(cap * 4), hlens = malloc((cap + NWBUF) * 4);
-    kind = malloc(cap), ok = malloc(cap + NWBUF);
-    if (!offs || !todo || !bit || !lens || !hlens || !kind || !ok) return 1;
+    if (list_alloc(4 * (PAGE / 50) + NWBUF) != 0) return 1;
+    todo = malloc((cap + NWBUF) * 8), bit = malloc((cap + NWBUF) * 8);
+    hlens = malloc((cap + NWBUF) * 4), ok = malloc(cap + NWBUF);
+    if (!todo || !bit || !hlens || !ok) return 1;
 
     /* the old flow over a copy of the damaged bytes, then the new one over the page */
     triage = 0;
@@ -305,9 +113,7 @@ int main(int argc, char **argv) {
 
     /* the sim's own count of what no rule can fix, from the pristine bytes; a rescued image is the one written */
     uint64_t c_multi = 0, c_length = 0, c_crlf = 0, first_dead[NWBUF];
-    for (uint32_t w = 0; w < NWBUF; ++w) first_dead[w] = UINT64_MAX; /* the wbuf's first header no rule fixes */
-    for (uint32_t id = 0; id < nitems; ++id)
-        if (dead[id] && at[id] < first_dead[at[id] / WBUF]) first_dead[at[id] / WBUF] = at[id];
+    first_dead_of(first_dead);
     for (uint32_t id = 0; id < nitems; ++id) {
         if (where[id] == GONE) continue;
         const uint8_t *im = page + where[id], *was_b = pristine + where[id];
@@ -315,14 +121,8 @@ int main(int argc, char **argv) {
             if (memcmp(im + 28, was_b + 28, size_of[id] - 28) != 0) ++failures;
             continue;
         }
-        uint32_t nflipped = 0;
         uint64_t which = 0;
-        for (uint32_t b = 28; b < size_of[id]; ++b)
-            for (uint32_t i = 0; i < 8; ++i)
-                if ((im[b] ^ was_b[b]) >> i & 1) {
-                    ++nflipped;
-                    which = 8ull * b + i;
-                }
+        const uint32_t nflipped = flipped_bits(im, was_b, size_of[id], &which);
         const int behind = at[id] > first_dead[at[id] / WBUF];
         if (nflipped >= 2) ++c_multi;
         else if (nflipped == 1 && behind && length_bit(which)) ++c_length;
@@ -330,7 +130,7 @@ int main(int argc, char **argv) {
         else ++failures; /* intact, one bit in front of every such header, or a suspect: it should have come back */
     }
     printf("triage_sim: %u items, %llu header-damaged, %llu with a length bit, %llu data-damaged, failures %d\n", nitems,
-           (unsigned long long)ndamaged, (unsigned long long)nlen, (unsigned long long)ndata, failures);
+           (unsigned long long)c.ndamaged, (unsigned long long)c.nlen, (unsigned long long)c.ndata, failures);
     printf("live=%llu lost_old=%llu lost_recover=%llu lost_headers=%llu lost_triage=%llu headers_repaired=%llu "
            "items_repaired=%llu suspects=%llu suspects_kept=%llu rounds=%d unrepairable=%llu multi=%llu "
            "behind_length=%llu behind_crlf=%llu\n",
@@ -340,7 +140,7 @@ int main(int argc, char **argv) {
            (unsigned long long)f.suspects, (unsigned long long)f.suspects_kept, f.rounds,
            (unsigned long long)(c_multi + c_length + c_crlf), (unsigned long long)c_multi,
            (unsigned long long)c_length, (unsigned long long)c_crlf);
-    free(offs); free(todo); free(bit); free(lens); free(hlens); free(kind); free(ok);
+    list_free(); free(todo); free(bit); free(hlens); free(ok);
     free(page);
     free(pristine);
     free(old);

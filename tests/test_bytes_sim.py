@@ -4,12 +4,9 @@ of one byte and bits of two bytes, played three ways over the same bytes: the
 reference's walk, the one call crc32c_recover_pages, and that call followed by
 crc32c_repair_bytes over its bad sane entries.  With the byte rule the page
 loses exactly what the sim's own CPU search says the rule cannot fix."""
-import re
-import subprocess
-
 import pytest
 
-from .test_integration import _NOGPU, _build_c
+from .test_integration import _build_c, _run_sim, _sim_fields
 
 FIELDS = ("live", "lost_reference", "lost_recover", "lost_bytes", "repaired", "samebyte", "unrepairable", "length",
           "twobyte", "unlisted")
@@ -21,19 +18,12 @@ def bytes_exe(tmp_path_factory):
 
 
 def test_bytes_sim_without_gpu(bytes_exe):
-    r = subprocess.run([bytes_exe], capture_output=True, text=True, env=_NOGPU, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "no gfx950 device" in r.stdout
+    assert "no gfx950 device" in _run_sim(bytes_exe)
 
 
 @pytest.mark.gpu
 def test_bytes_sim_loses_only_what_the_rule_cannot_fix(bytes_exe):
-    r = subprocess.run([bytes_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search("^" + " ".join(f"{f}=(\\d+)" for f in FIELDS) + "$", r.stdout, re.M)
-    assert m, r.stdout
-    f = dict(zip(FIELDS, map(int, m.groups())))
+    f = _sim_fields(_run_sim(bytes_exe, gpu=True), FIELDS)
     assert f["lost_bytes"] == f["unrepairable"] == f["length"] + f["twobyte"] + f["unlisted"]
     assert f["lost_bytes"] < f["lost_recover"] < f["lost_reference"]
     assert f["repaired"] == f["lost_recover"] - f["lost_bytes"] > 0

@@ -8,22 +8,13 @@ loses what scrub_sim.c reports.  Every rescued image equals its pristine bytes
 from byte 28 and the log replayed on the damaged bytes gives the page (both
 are failures of the run inside the sim).  Without a GPU the call reports
 CRC32C_ENODEV and writes nothing."""
-import re
-import subprocess
-
 import pytest
 
-from .test_integration import _NOGPU, _build_c
+from .test_integration import _build_c, _run_sim, _sim_fields
 from .test_scrub_sim import FIELDS as SCRUB_FIELDS
 
 FIELDS = ("live", "lost_scrub", "unrepairable_scrub", "lost_gaps", "unrepairable_gaps", "multi", "dead", "behind_lost",
           "rounds_scrub", "rounds_gaps", "headers_repaired", "items_repaired", "nflips", "complete")
-
-
-def _fields(stdout, fields):
-    m = re.search("^" + " ".join(f"{f}=(\\d+)" for f in fields) + "$", stdout, re.M)
-    assert m, stdout
-    return dict(zip(fields, map(int, m.groups())))
 
 
 @pytest.fixture(scope="module")
@@ -37,22 +28,15 @@ def scrub_exe(tmp_path_factory):
 
 
 def test_gaps_sim_without_gpu(gaps_exe):
-    r = subprocess.run([gaps_exe], capture_output=True, text=True, env=_NOGPU, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "no gfx950 device" in r.stdout
+    assert "no gfx950 device" in _run_sim(gaps_exe)
 
 
 @pytest.mark.gpu
 def test_gaps_sim_loses_only_what_the_rule_cannot_fix(gaps_exe, scrub_exe):
-    r = subprocess.run([gaps_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    f = _fields(r.stdout, FIELDS)
+    f = _sim_fields(_run_sim(gaps_exe, gpu=True), FIELDS)
     assert f["lost_gaps"] == f["unrepairable_gaps"] == f["multi"] + f["dead"] + f["behind_lost"]
     assert f["lost_gaps"] < f["lost_scrub"] == f["unrepairable_scrub"]
     assert f["complete"] == 1 and f["nflips"] == f["headers_repaired"] + f["items_repaired"]
     assert f["rounds_gaps"] >= 2 and f["rounds_scrub"] >= 2
     assert f["behind_lost"] < f["lost_scrub"] - f["multi"] - f["dead"]
-    s = subprocess.run([scrub_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    assert s.returncode == 0, s.stdout + s.stderr
-    assert _fields(s.stdout, SCRUB_FIELDS)["lost_scrub"] == f["lost_scrub"]
+    assert _sim_fields(_run_sim(scrub_exe, gpu=True), SCRUB_FIELDS)["lost_scrub"] == f["lost_scrub"]

@@ -34,6 +34,28 @@ def _build_c(tmp_path_factory, name):
     return exe
 
 
+_NOGPU = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
+
+
+def _run_sim(exe, *args, gpu=False):
+    """Runs a sim with --gpu, or without it on its no-GPU leg; returns its
+    stdout.  The run itself must have worked: exit status 0."""
+    if gpu:
+        r = subprocess.run([exe, "--gpu", *args], capture_output=True, text=True, timeout=300)
+    else:
+        r = subprocess.run([exe, *args], capture_output=True, text=True, env=_NOGPU, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout
+
+
+def _sim_fields(stdout, fields):
+    """The sim's line of counts, `name=<int> ...` in exactly this order, as a dict."""
+    m = re.search("^" + " ".join(f"{f}=(\\d+)" for f in fields) + "$", stdout, re.M)
+    assert m, stdout
+    return dict(zip(fields, map(int, m.groups())))
+
+
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
     return _build_c(tmp_path_factory, "storage_sim")
@@ -115,9 +137,6 @@ def queue_exe(tmp_path_factory):
 @pytest.fixture(scope="module")
 def extstore_exe(tmp_path_factory):
     return _build_c(tmp_path_factory, "extstore_sim")
-
-
-_NOGPU = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
 
 
 def test_queue_sim_without_gpu(queue_exe):

@@ -3,11 +3,9 @@ headers were damaged on flash, through the one call crc32c_recover_pages and a
 single rescue loop over its merged list.  It loses only the images whose own
 header was hit, and reaches and salvages exactly what crc32c_verify_pages
 followed by crc32c_salvage_pages does."""
-import subprocess
-
 import pytest
 
-from .test_integration import _NOGPU, _build_c
+from .test_integration import _build_c, _run_sim
 from .test_salvage_sim import _counts
 
 
@@ -22,24 +20,16 @@ def salvage_exe(tmp_path_factory):
 
 
 def test_recover_sim_without_gpu(recover_exe):
-    r = subprocess.run([recover_exe], capture_output=True, text=True, env=_NOGPU, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "no gfx950 device" in r.stdout
+    assert "no gfx950 device" in _run_sim(recover_exe)
 
 
 @pytest.mark.gpu
 def test_recover_sim_loses_only_the_damaged_images(recover_exe, salvage_exe):
-    r = subprocess.run([recover_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    f = _counts(r.stdout)
+    f = _counts(_run_sim(recover_exe, gpu=True))
     assert f["lost"] == f["damaged"] > 0
     assert f["reached"] + f["salvaged"] + f["lost"] == f["live"]
 
     # the two-call flow on the same page and damage
-    r2 = subprocess.run([salvage_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    print(r2.stdout)
-    assert r2.returncode == 0, r2.stdout + r2.stderr
-    g = _counts(r2.stdout)
+    g = _counts(_run_sim(salvage_exe, gpu=True))
     assert (g["live"], g["damaged"]) == (f["live"], f["damaged"])
     assert (f["reached"], f["salvaged"]) == (g["reached"], g["salvaged"]) and f["salvaged"] > 0

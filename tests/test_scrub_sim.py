@@ -6,12 +6,9 @@ in the same run; every rescued image equals its pristine bytes from byte 28 and
 the log replayed on the damaged bytes gives the page (both are failures of the
 run inside the sim).  Without a GPU the call reports CRC32C_ENODEV and writes
 nothing, not one word of its struct."""
-import re
-import subprocess
-
 import pytest
 
-from .test_integration import _NOGPU, _build_c
+from .test_integration import _build_c, _run_sim, _sim_fields
 
 FIELDS = ("live", "lost_written_out", "lost_scrub", "calls_written_out", "headers_repaired", "items_repaired", "rounds",
           "nflips", "complete", "unrepairable", "multi", "behind_length", "behind_crlf")
@@ -23,19 +20,12 @@ def scrub_exe(tmp_path_factory):
 
 
 def test_scrub_sim_without_gpu(scrub_exe):
-    r = subprocess.run([scrub_exe], capture_output=True, text=True, env=_NOGPU, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "no gfx950 device" in r.stdout
+    assert "no gfx950 device" in _run_sim(scrub_exe)
 
 
 @pytest.mark.gpu
 def test_scrub_sim_loses_only_what_no_rule_can_fix(scrub_exe):
-    r = subprocess.run([scrub_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search("^" + " ".join(f"{f}=(\\d+)" for f in FIELDS) + "$", r.stdout, re.M)
-    assert m, r.stdout
-    f = dict(zip(FIELDS, map(int, m.groups())))
+    f = _sim_fields(_run_sim(scrub_exe, gpu=True), FIELDS)
     assert f["lost_scrub"] == f["unrepairable"] == f["multi"] + f["behind_length"] + f["behind_crlf"]
     assert f["lost_scrub"] == f["lost_written_out"]
     assert f["complete"] == 1 and f["nflips"] == f["headers_repaired"] + f["items_repaired"]

@@ -4,12 +4,9 @@ and through the new one, crc32c_triage_pages in crc32c_recover_pages' place and
 the filtered suspects added to the repair list.  At the end the new flow loses
 exactly what the sim's own count from the pristine bytes and its own layout
 says no rule can fix now, and fewer than the old flow lost in the same run."""
-import re
-import subprocess
-
 import pytest
 
-from .test_integration import _NOGPU, _build_c
+from .test_integration import _build_c, _run_sim, _sim_fields
 
 FIELDS = ("live", "lost_old", "lost_recover", "lost_headers", "lost_triage", "headers_repaired", "items_repaired",
           "suspects", "suspects_kept", "rounds", "unrepairable", "multi", "behind_length", "behind_crlf")
@@ -21,19 +18,12 @@ def triage_exe(tmp_path_factory):
 
 
 def test_triage_sim_without_gpu(triage_exe):
-    r = subprocess.run([triage_exe], capture_output=True, text=True, env=_NOGPU, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "no gfx950 device" in r.stdout
+    assert "no gfx950 device" in _run_sim(triage_exe)
 
 
 @pytest.mark.gpu
 def test_triage_sim_loses_only_what_no_rule_can_fix(triage_exe):
-    r = subprocess.run([triage_exe, "--gpu"], capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    m = re.search("^" + " ".join(f"{f}=(\\d+)" for f in FIELDS) + "$", r.stdout, re.M)
-    assert m, r.stdout
-    f = dict(zip(FIELDS, map(int, m.groups())))
+    f = _sim_fields(_run_sim(triage_exe, gpu=True), FIELDS)
     assert f["lost_triage"] == f["unrepairable"] == f["multi"] + f["behind_length"] + f["behind_crlf"]
     assert f["lost_triage"] < f["lost_old"]
     assert f["lost_triage"] < f["lost_headers"] < f["lost_recover"]
