@@ -39,10 +39,9 @@
 #include "k_blocks.h"  // K4
 #include "k_lines.h"   // K5: k_lines, k_fix, k_census
 #include "k_walk.h"    // k_gather_offs, k_scatter_ok, k_chain, k_walk
-#include "k_salvage.h" // crc32c_salvage_pages: k_salvage_regions, k_salvage_scan, k_salvage_pick
-#include "k_recover.h" // crc32c_recover_pages: k_recover_regions, k_recover_merge
+#include "k_salvage.h" // crc32c_salvage_pages: k_salvage_regions, k_salvage_scan, k_salvage_pick (the triage's too)
+#include "k_recover.h" // crc32c_recover_pages, crc32c_triage_pages: k_recover_regions, k_recover_merge
 #include "k_repair.h"  // crc32c_repair_items: k_repair_count, k_repair_emit, k_repair_search, k_repair_apply
 #include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply
-#include "k_triage.h"  // crc32c_triage_pages: k_triage_pick, k_triage_merge
-#include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_log
+#include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_gaps, k_scrub_gap_merge, k_scrub_log
 #include "k_repair_bytes.h"  // crc32c_repair_bytes: k_repair_bytes_search, k_repair_bytes_apply

@@ -11,15 +11,25 @@
 //                      from aligned 16-B loads, sane + CRLF = a candidate;
 //   (the candidates' CRCs: the item kernels, run_items<1> over the list)
 //   k_salvage_pick     per piece, the verified candidates that start at or
-//                      after the end of the last one kept.
+//                      after the end of the last one kept; for
+//                      crc32c_triage_pages (SUSPECTS) also the failing ones
+//                      that the cursor of the rule reaches.
 // Regions, scan and pick each run twice around a k_scan32, as the walk does:
 // count, scan the counts, emit in ascending order.
+// The page calls behind the salvage (k_recover.h, k_scrub.h) are built from
+// the same parts: what their per-piece kernels share stands first here
+// (wave_rank, sane_ntotal, sv_lower_bound and the wave helpers), and TileRun,
+// a piece's tile bookkeeping, serves both regions kernels.
 #pragma once
 
 #include "k_plan.h"
 #include "salvage_geom.h"
 
 namespace mcrc_dev {
+
+// The kinds the pick gives an entry (the walk's own verdicts are 0, 1, ...)
+constexpr uint8_t kKindSalvaged = 4;  // CRC32C_ITEM_SALVAGED
+constexpr uint8_t kKindSuspect = 6;   // CRC32C_ITEM_SUSPECT
 
 // A tile: the eligible offsets [lo, hi) of one aligned block, in a piece that
 // ends at pe.
@@ -83,6 +93,23 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
     return (uint64_t)__shfl((unsigned long long)v, src, 64);
 }
+// This lane's rank in a ballot: the set lanes below it.
+__device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// The length the header at o claims: its ITEM_ntotal when it is sane
+// (crc32c_verify_items' rule, item_desc), else 0.  h: the header as read, when
+// 48 bytes of the buffer lie at o (room); the second form looks and reads.
+__device__ __forceinline__ uint32_t sane_ntotal(const SpanArgs &a, uint64_t o, const ItemHdr &h, bool room) {
+    return item_desc(a, o, h, room).sane ? (uint32_t)h.ntotal(a.cfl) : 0u;
+}
+__device__ __forceinline__ uint32_t sane_ntotal(const SpanArgs &a, uint64_t o) {
+    const bool room = o <= a.base_bytes && a.base_bytes - o >= 48;
+    ItemHdr h{0u, 0u, 0u, 0u};
+    if (room) h = parse_hdr(a.base + o);
+    return sane_ntotal(a, o, h, room);
+}
 
 // *p0 += the workgroup's sum of a (and p0[1] += that of b): one atomic per
 // word and workgroup.  (Same-address atomics serialise in L2, about 8 ns each:
@@ -104,6 +131,74 @@ __device__ __forceinline__ void block_add64(unsigned long long *p0, uint64_t a, 
         if (sh[1]) atomicAdd(p0 + 1, sh[1]);
     }
 }
+
+// One piece's tiles in a regions kernel (k_salvage_regions, and
+// k_recover_regions of k_recover.h): the kernel finds each round's ranges, one
+// per lane, by its own rule; what becomes of them is the same.  w: the piece,
+// ending at pe; first: prefix[w] (EMIT); j: the lane.
+template <bool EMIT>
+struct TileRun {
+    const SalvageArgs &s;
+    SalvageTile *tiles;
+    uint64_t cap, w, pe, first;
+    uint32_t j;
+    uint64_t scanned = 0;        // this lane's eligible offsets
+    uint32_t run = 0, mine = 0;  // tiles written so far (wave-uniform) / counted by this lane
+    uint32_t nreg = 0;           // ranges so far (wave-uniform)
+
+    // the tiles of one round's ranges (r, nt tiles, per lane): every range in turn, its tiles by all lanes
+    __device__ __forceinline__ void put(const mcrc::SalvageRange &r, uint32_t nt) {
+        const uint32_t inc = wave_incl_scan(nt, j);
+        unsigned long long m = __ballot(nt != 0);
+        while (m) {
+            const int src = __ffsll(m) - 1;
+            m &= m - 1;
+            const uint64_t lo = shfl64(r.lo, src), hi = shfl64(r.hi, src);
+            const uint32_t n_r = __shfl(nt, src, 64), at = run + __shfl(inc - nt, src, 64);
+            for (uint32_t k = j; k < n_r; k += 64) {
+                const mcrc::SalvageRange t = mcrc::salvage_tile(lo, hi, s.ba, k);
+                const uint64_t idx = first + at + k;
+                if (idx < cap) tiles[idx] = SalvageTile{t.lo, t.hi, pe};
+            }
+        }
+        run += __shfl(inc, 63, 64);
+    }
+    // EMIT, and the count pass kept all of the piece's ranges: its tiles are cut from those
+    __device__ __forceinline__ bool from_kept() {
+        if (!EMIT || s.nregs[w] > kSvSlots) return false;
+        mcrc::SalvageRange r{0, 0};
+        if (j < s.nregs[w]) r = {s.slots[(w * kSvSlots + j) * 2], s.slots[(w * kSvSlots + j) * 2 + 1]};
+        put(r, (uint32_t)mcrc::salvage_ntiles(r.lo, r.hi, s.ba));
+        return true;
+    }
+    // one round: this lane's range r (in: it has one).  EMIT: its tiles are
+    // written; else counted, and the piece's first kSvSlots ranges kept for the emit pass
+    __device__ __forceinline__ void round(mcrc::SalvageRange r, bool in) {
+        if (!in) r.hi = r.lo;
+        const uint32_t nt = (uint32_t)mcrc::salvage_ntiles(r.lo, r.hi, s.ba);
+        if (EMIT) {
+            put(r, nt);
+            return;
+        }
+        scanned += r.hi - r.lo;
+        mine += nt;
+        const unsigned long long hm = __ballot(nt != 0);
+        const uint32_t at = nreg + wave_rank(hm);
+        if (nt != 0 && at < kSvSlots) {
+            s.slots[(w * kSvSlots + at) * 2] = r.lo;
+            s.slots[(w * kSvSlots + at) * 2 + 1] = r.hi;
+        }
+        nreg += (uint32_t)__popcll(hm);
+    }
+    // behind the piece's last round (the count pass): nregs[w], cnt[w], the lane's share of the scanned
+    __device__ __forceinline__ void done(uint32_t *cnt, uint64_t &all_scanned) {
+        if (EMIT) return;
+        if (j == 0) s.nregs[w] = nreg;
+        wave_sum(mine);
+        if (j == 0) cnt[w] = mine;
+        all_scanned += scanned;
+    }
+};
 
 // Regions.  One wave per piece [ps, pe).  The piece's list entries are found by
 // two binary searches; "entry" 0 of the piece is its head, the bytes in front
@@ -132,33 +227,9 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_salvage_regions(SpanArgs a,
     uint64_t all_scanned = 0;  // this lane's share of the eligible offsets of the wave's pieces
     for (uint64_t w = (uint64_t)blockIdx.x * kWalkWaves + wave; w < s.nw; w += (uint64_t)gridDim.x * kWalkWaves) {
         const uint64_t ps = w * a.region, pe = mcrc::salvage_piece_end(w, a.region, a.base_bytes);
-        const uint64_t first = EMIT ? prefix[w] : 0;
-        uint64_t carry = ps, scanned = 0;  // carry: the covered bytes end here (wave-uniform)
-        uint32_t run = 0, mine = 0;        // tiles written so far (wave-uniform) / counted by this lane
-        uint32_t nreg = 0;                 // ranges so far (wave-uniform)
-        // the tiles of one round's ranges (r, nt tiles, per lane): every range in turn, its tiles by all lanes
-        auto put = [&](const mcrc::SalvageRange &r, uint32_t nt) {
-            const uint32_t inc = wave_incl_scan(nt, j);
-            unsigned long long m = __ballot(nt != 0);
-            while (m) {
-                const int src = __ffsll(m) - 1;
-                m &= m - 1;
-                const uint64_t lo = shfl64(r.lo, src), hi = shfl64(r.hi, src);
-                const uint32_t n_r = __shfl(nt, src, 64), at = run + __shfl(inc - nt, src, 64);
-                for (uint32_t k = j; k < n_r; k += 64) {
-                    const mcrc::SalvageRange t = mcrc::salvage_tile(lo, hi, s.ba, k);
-                    const uint64_t idx = first + at + k;
-                    if (idx < cap) tiles[idx] = SalvageTile{t.lo, t.hi, pe};
-                }
-            }
-            run += __shfl(inc, 63, 64);
-        };
-        if (EMIT && s.nregs[w] <= kSvSlots) {  // the count pass kept them all: no header is read again
-            mcrc::SalvageRange r{0, 0};
-            if (j < s.nregs[w]) r = {s.slots[(w * kSvSlots + j) * 2], s.slots[(w * kSvSlots + j) * 2 + 1]};
-            put(r, (uint32_t)mcrc::salvage_ntiles(r.lo, r.hi, s.ba));
-            continue;
-        }
+        TileRun<EMIT> tr{s, tiles, cap, w, pe, EMIT ? prefix[w] : 0, j};
+        if (tr.from_kept()) continue;  // (no header is read again)
+        uint64_t carry = ps;  // the covered bytes end here (wave-uniform)
         const uint64_t i0 = s.nwalked ? sv_lower_bound(s.walked, s.nwalked, ps) : 0;
         const uint64_t i1 = s.nwalked ? sv_lower_bound(s.walked, s.nwalked, pe) : 0;
         const uint64_t nv = i1 - i0 + 1;  // the head and the entries
@@ -170,12 +241,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_salvage_regions(SpanArgs a,
                 if (v) {
                     const uint64_t i = i0 + v - 1, o = s.walked[i];
                     e = o;
-                    if (s.walked_ok[i]) {
-                        const bool hdr_ok = o <= a.base_bytes && a.base_bytes - o >= 48;
-                        ItemHdr h{0u, 0u, 0u, 0u};
-                        if (hdr_ok) h = parse_hdr(a.base + o);
-                        if (item_desc(a, o, h, hdr_ok).sane) e = o + h.ntotal(a.cfl);
-                    }
+                    if (s.walked_ok[i]) e = o + sane_ntotal(a, o);
                 }
                 if (i0 + v < i1) nxt = s.walked[i0 + v];
             }
@@ -187,31 +253,9 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_salvage_regions(SpanArgs a,
             }
             if (carry > pm) pm = carry;
             carry = shfl64(pm, 63);
-            mcrc::SalvageRange r = mcrc::salvage_cut(pm, nxt, ps, pe);
-            if (!in) r.hi = r.lo;
-            const uint32_t nt = (uint32_t)mcrc::salvage_ntiles(r.lo, r.hi, s.ba);
-            if (EMIT) {
-                put(r, nt);
-                continue;
-            }
-            scanned += r.hi - r.lo;
-            mine += nt;
-            // the piece's first kSvSlots ranges are kept for the emit pass
-            const unsigned long long hm = __ballot(nt != 0);
-            const uint32_t at = nreg + __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32),
-                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
-            if (nt != 0 && at < kSvSlots) {
-                s.slots[(w * kSvSlots + at) * 2] = r.lo;
-                s.slots[(w * kSvSlots + at) * 2 + 1] = r.hi;
-            }
-            nreg += (uint32_t)__popcll(hm);
+            tr.round(mcrc::salvage_cut(pm, nxt, ps, pe), in);
         }
-        if (!EMIT && j == 0) s.nregs[w] = nreg;
-        if (!EMIT) {
-            wave_sum(mine);
-            if (j == 0) cnt[w] = mine;
-            all_scanned += scanned;
-        }
+        tr.done(cnt, all_scanned);
     }
     if constexpr (!EMIT) block_add64(s.ctr + kSvScanned, all_scanned, 0ull, j);
 }
@@ -355,17 +399,40 @@ __global__ __launch_bounds__(256) void k_salvage_scan(SpanArgs a, SalvageArgs s,
     if constexpr (!EMIT) block_add64(s.ctr + kSvCand, all_cand, all_work, j);  // (kSvWork = kSvCand + 1)
 }
 
+// What the pick needs to keep suspects (crc32c_triage_pages): the walk's list
+// and the scan of its per-piece counts (piece w's entries are [wpre[w],
+// wpre[w + 1])), the per-piece counts of the found, and the kind bytes.  The
+// salvage's and the recover call's launches pass it empty.
+struct PickSuspects {
+    const uint64_t *walked;
+    const uint32_t *wpre;
+    uint32_t *fcnt;
+    uint8_t *okind;
+};
+
 // The pick.  One wave per piece over its candidates (two binary searches), 64
 // a round; the verified ones are gone through in order by the whole wave (the
 // state, the end of the last image kept, is wave-uniform), and a candidate is
-// kept when it starts at or after that end.
-//   EMIT false: cnt[w] = the piece's kept candidates;
-//   EMIT true:  kept candidate prefix[w] + r is written to out, when below cap.
-template <bool EMIT>
+// kept (found) when it starts at or after that end.
+// SUSPECTS: a failing candidate is picked too, as a suspect, when
+//   it starts at or after the end that the verified candidates below it have
+//     produced (each lane keeps the end as of the lanes before it: `mine`; a
+//     suspect never moves the end, its length is not proven);
+//   it is no entry of the walk's list (a walked entry with verdict 0 that is
+//     itself a failing candidate is in the list already, as kind 0): a search
+//     in the piece's own entries.
+// (Outside the covered set it is by being a candidate: the scan looks at
+// eligible offsets only.)  Without SUSPECTS none of that is compiled in.
+//   EMIT false: cnt[w] = the piece's picked candidates (SUSPECTS: and
+//               t.fcnt[w] = the found among them);
+//   EMIT true:  picked candidate prefix[w] + r is written to out, when below
+//               cap (SUSPECTS: and its kind, kKindSalvaged or kKindSuspect, to t.okind).
+template <bool EMIT, bool SUSPECTS>
 __global__ __launch_bounds__(64 * kWalkWaves) void k_salvage_pick(const uint64_t *cand, const uint32_t *cand_nt,
                                                                   const uint8_t *ok, uint64_t ncand, uint64_t wbuf,
                                                                   uint64_t base_bytes, uint64_t nw, uint32_t *cnt,
-                                                                  const uint32_t *prefix, uint64_t *out, uint64_t cap) {
+                                                                  const uint32_t *prefix, uint64_t *out, uint64_t cap,
+                                                                  PickSuspects t) {
     MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
     const uint32_t j = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -373,15 +440,22 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_salvage_pick(const uint64_t
         const uint64_t ps = w * wbuf, pe = mcrc::salvage_piece_end(w, wbuf, base_bytes);
         const uint64_t c0 = sv_lower_bound(cand, ncand, ps), c1 = sv_lower_bound(cand, ncand, pe);
         const uint64_t first = EMIT ? prefix[w] : 0;
+        uint64_t i0 = 0, nwk = 0;  // the piece's walked entries
+        if constexpr (SUSPECTS) {
+            i0 = t.wpre[w];
+            nwk = t.wpre[w + 1] - i0;
+        }
         uint64_t end = 0;
-        uint32_t kept = 0;
+        uint32_t picked = 0, kept = 0;
         for (uint64_t cc = c0; cc < c1; cc += 64) {
             const uint64_t i = cc + j;
             const bool in = i < c1;
             const uint64_t o = in ? cand[i] : 0;
             const uint32_t nt = in ? cand_nt[i] : 0u;
-            bool keep = false;
-            unsigned long long m = __ballot(in && ok[in ? i : c0] != 0);
+            const bool good = in && ok[in ? i : c0] != 0;
+            uint64_t mine = end;  // the end as of the lanes before this one
+            bool keep = false, suspect = false;
+            unsigned long long m = __ballot(good);
             while (m) {
                 const int src = __ffsll(m) - 1;
                 m &= m - 1;
@@ -389,18 +463,32 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_salvage_pick(const uint64_t
                 if (so >= end) {
                     end = so + __shfl(nt, src, 64);
                     keep |= (int)j == src;
+                    if (SUSPECTS && (int)j > src) mine = end;
                 }
             }
-            const unsigned long long km = __ballot(keep);
-            if (EMIT && keep) {
-                const uint64_t idx = first + kept +
-                                     __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32),
-                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
-                if (idx < cap) out[idx] = o;
+            unsigned long long pm = __ballot(keep);  // the picked: the kept ...
+            if constexpr (SUSPECTS) {  // ... and the suspects
+                suspect = in && !good && o >= mine;
+                if (suspect && nwk) {
+                    const uint64_t k = sv_lower_bound(t.walked + i0, nwk, o);
+                    suspect = !(k < nwk && t.walked[i0 + k] == o);
+                }
+                kept += (uint32_t)__popcll(pm);
+                pm |= __ballot(suspect);
             }
-            kept += (uint32_t)__popcll(km);
+            if (EMIT && (keep || suspect)) {
+                const uint64_t idx = first + picked + wave_rank(pm);
+                if (idx < cap) {
+                    out[idx] = o;
+                    if constexpr (SUSPECTS) t.okind[idx] = keep ? kKindSalvaged : kKindSuspect;
+                }
+            }
+            picked += (uint32_t)__popcll(pm);
         }
-        if (!EMIT && j == 0) cnt[w] = kept;
+        if (!EMIT && j == 0) {
+            cnt[w] = picked;
+            if constexpr (SUSPECTS) t.fcnt[w] = kept;
+        }
     }
 }
 

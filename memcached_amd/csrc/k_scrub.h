@@ -1,6 +1,6 @@
 // k_scrub.h -- crc32c_scrub_pages: the two list rules a caller of the repair
 // flow ran on the host between crc32c_triage_pages and the repair calls, and
-// the flip log, as kernels over the merged list where k_triage_merge left it
+// the flip log, as kernels over the merged list where k_recover_merge left it
 // (ascending by offset, whole: the scrub sizes its scratch by the list).
 //
 //   k_scrub_headers  the list for crc32c_repair_headers:
@@ -8,7 +8,9 @@
 //                    the end of its last walked entry (kinds 4 and 6 are no
 //                    walked entries), or the piece's start when it has none --
 //                    when that entry is not kind 0 and 48 bytes of the piece
-//                    remain there;
+//                    remain there (over the second list of CRC32C_SCRUB_GAPS a
+//                    gap entry is listed as a kind-0 entry is, and the walk
+//                    end takes its place in front of the gap starts behind it);
 //   k_scrub_items    the list for crc32c_repair_items:
 //                    every kind-0 entry with a length, and every suspect that
 //                    ends at or before the next proven entry (kind 1 or 4) and
@@ -31,18 +33,15 @@
 //                         list, ascending (a gap start is no entry's offset:
 //                         no ties), with two kind arrays: a gap entry is
 //                         kKindGap for the headers, and for the items
-//                         kKindSuspect when it has a length, else kKindGap;
-//   k_scrub_headers_gaps  k_scrub_headers over the second list: a gap entry is
-//                         listed as a kind-0 entry is, and the walk end takes
-//                         its place in front of the gap starts behind it.
-// k_scrub_items runs over the second list as it is: a gap entry with a length
-// goes through its filter as the suspect its kind says, one without is of no
-// kind it takes.  (k_scrub_headers_gaps is a kernel of its own: the older
-// kernels' instruction streams are kept as they are, as for k_triage_pick.)
+//                         kKindSuspect when it has a length, else kKindGap.
+// Both list kernels run over the second list as they do over the triage's own:
+// k_scrub_headers by the rule above, and in k_scrub_items a gap entry with a
+// length goes through the filter as the suspect its kind says, one without is
+// of no kind it takes.
 // A gap start lies in its entry's piece, so both rules stay piece-local.
 #pragma once
 
-#include "k_triage.h"
+#include "k_recover.h"
 
 namespace mcrc_dev {
 
@@ -57,59 +56,9 @@ struct ScrubList {
     uint64_t n;
 };
 
-__device__ __forceinline__ uint32_t scrub_rank(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-//   EMIT false: cnt[w] = the piece's entries of the header list;
-//   EMIT true:  entry prefix[w] + r is written to out, when below cap.
-template <bool EMIT>
-__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_headers(ScrubList l, uint64_t wbuf, uint64_t base_bytes,
-                                                                   uint64_t nw, uint32_t *cnt, const uint32_t *prefix,
-                                                                   uint64_t *out, uint64_t cap) {
-    MCRC_VGPR_FLOOR();  // (several workgroups per CU: crc32c_device.h)
-    const uint32_t j = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (uint64_t w = (uint64_t)blockIdx.x * kWalkWaves + wave; w < nw; w += (uint64_t)gridDim.x * kWalkWaves) {
-        const uint64_t ps = w * wbuf, pe = mcrc::salvage_piece_end(w, wbuf, base_bytes);
-        const uint64_t k0 = sv_lower_bound(l.offs, l.n, ps), k1 = sv_lower_bound(l.offs, l.n, pe);
-        const uint64_t first = EMIT ? prefix[w] : 0;
-        uint64_t end = ps;   // the walk end: behind the last walked entry
-        uint32_t last = 1u;  // that entry's kind (none: as a good one)
-        uint32_t listed = 0;
-        for (uint64_t kk = k0; kk < k1; kk += 64) {
-            const uint64_t i = kk + j;
-            const bool in = i < k1;
-            const uint64_t o = in ? l.offs[i] : 0;
-            const uint32_t len = in ? l.lens[i] : 0u;
-            const uint32_t kd = in ? l.kind[i] : (uint32_t)kKindSalvaged;
-            const bool zero = in && kd == 0u;
-            const unsigned long long zm = __ballot(zero);
-            if (EMIT && zero) {
-                const uint64_t idx = first + listed + scrub_rank(zm);
-                if (idx < cap) out[idx] = o;
-            }
-            listed += (uint32_t)__popcll(zm);
-            const unsigned long long wm = __ballot(in && kd != kKindSalvaged && kd != kKindSuspect);
-            if (wm) {
-                const int src = 63 - __clzll((long long)wm);
-                last = (uint32_t)__shfl((int)kd, src, 64);
-                end = shfl64(o + len, src);
-            }
-        }
-        // (a kind-0 entry is listed as itself; behind a good one every kind-0 entry of the piece lies in front of end)
-        const bool take = last != 0u && end >= ps && end <= pe && pe - end >= 48;
-        if (EMIT) {
-            if (take && j == 0 && first + listed < cap) out[first + listed] = end;
-        } else if (j == 0) {
-            cnt[w] = listed + (uint32_t)take;
-        }
-    }
-}
-
 // The greedy chain of the suspects kept is sequential, but only along the
 // suspects that end in time: the wave goes through those in order, as
-// k_triage_pick goes through the verified candidates.  The next proven entry
+// k_salvage_pick goes through the verified candidates.  The next proven entry
 // behind a lane's own is the first one above it in the round's ballot, or the
 // first one of the rounds behind it (`nxt`, looked for once per proven entry:
 // the search resumes where it last ended).
@@ -172,7 +121,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_items(ScrubList l, ui
             const bool take = keep || (in && kd == 0u && len != 0u);
             const unsigned long long tm = __ballot(take);
             if (EMIT && take) {
-                const uint64_t idx = first + listed + scrub_rank(tm);
+                const uint64_t idx = first + listed + wave_rank(tm);
                 if (idx < cap) out[idx] = o;
             }
             listed += (uint32_t)__popcll(tm);
@@ -214,11 +163,11 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_gaps(SpanArgs a, Scru
             }
             const unsigned long long gm = __ballot(gap);
             if (EMIT && gap) {
-                const uint64_t idx = first + listed + scrub_rank(gm);
+                const uint64_t idx = first + listed + wave_rank(gm);
                 if (idx < g.cap) {
                     const ItemHdr h = parse_hdr(a.base + e);
                     g.offsets[idx] = e;
-                    g.lens[idx] = item_desc(a, e, h, true).sane ? (uint32_t)h.ntotal(a.cfl) : 0u;
+                    g.lens[idx] = sane_ntotal(a, e, h, true);
                 }
             }
             listed += (uint32_t)__popcll(gm);
@@ -247,16 +196,19 @@ __global__ __launch_bounds__(256) void k_scrub_gap_merge(ScrubList l, const uint
     }
 }
 
-// k_scrub_headers over the second list.  A gap entry is listed as a kind-0
-// entry is and is no walked entry.  The walk end lies in front of the gap
-// starts behind it, so it is found first, in a pass over the kinds; the
-// listing pass then leaves its place free (`below` entries in front of it) and
-// moves the entries behind it up by one.  A walk end at which a gap entry
-// stands is listed once, as that entry.
+// The header list, over the triage's list or the second list.  A gap entry
+// (kKindGap: the second list only) is listed as a kind-0 entry is and is no
+// walked entry.  The walk end lies in front of the gap starts behind it, so it
+// is found first, in a pass over the kinds; the listing pass then leaves its
+// place free (`below` entries in front of it) and moves the entries behind it
+// up by one.  A walk end at which a gap entry stands is listed once, as that
+// entry.  (Over a list without gap entries that test never fires, and behind a
+// good last walked entry every kind-0 entry of the piece lies in front of the
+// walk end: below == listed, the walk end comes last.)
 //   EMIT false: cnt[w] = the piece's entries of the header list;
 //   EMIT true:  entry prefix[w] + r is written to out, when below cap.
 template <bool EMIT>
-__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_headers_gaps(ScrubList l, uint64_t wbuf, uint64_t base_bytes,
+__global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_headers(ScrubList l, uint64_t wbuf, uint64_t base_bytes,
                                                                         uint64_t nw, uint32_t *cnt,
                                                                         const uint32_t *prefix, uint64_t *out,
                                                                         uint64_t cap) {
@@ -294,7 +246,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void k_scrub_headers_gaps(ScrubLis
             const bool zero = in && (kd == 0u || kd == kKindGap);
             const unsigned long long zm = __ballot(zero);
             if (EMIT && zero) {
-                const uint64_t idx = first + listed + scrub_rank(zm) + (take && o > end ? 1u : 0u);
+                const uint64_t idx = first + listed + wave_rank(zm) + (take && o > end ? 1u : 0u);
                 if (idx < cap) out[idx] = o;
             }
             listed += (uint32_t)__popcll(zm);
@@ -332,7 +284,7 @@ __global__ __launch_bounds__(kScrubLogThreads) void k_scrub_log(const uint64_t *
             all += sh[k];
         }
         __syncthreads();
-        const uint64_t idx = carry + before + scrub_rank(m);
+        const uint64_t idx = carry + before + wave_rank(m);
         if (hit && idx < cap) {
             flip_offsets[idx] = list[i];
             flip_bits[idx] = bit[i];

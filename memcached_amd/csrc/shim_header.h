@@ -47,7 +47,7 @@ int header_stages(Device &d, hipStream_t st, const mcrc_dev::SpanArgs &a, uint64
     HIP_OK(hipEventRecord(d.ev0, st));
     hipLaunchKernelGGL(mcrc_dev::k_header_variants<false>, grid, block, 0, st, a, h);
     HIP_OK(hipEventRecord(d.ev1, st));
-    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)h.cnt, n, h.pre);
+    scan32(st, h.cnt, n, h.pre);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(hc, h.ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));

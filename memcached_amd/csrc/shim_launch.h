@@ -11,6 +11,12 @@ std::atomic<uint64_t> g_small_max{mcrc_dev::kSmallMax};  // crc32c_set_small_max
 uint64_t small_max() { return g_small_max.load(std::memory_order_relaxed); }
 std::atomic<uint64_t> g_k1_tail_min{mcrc_dev::kK1TailMinSteps};  // crc32c_set_k1_tail_min
 
+// out[0..n] = the exclusive scan of in[0..n) and its total: the step between a
+// count pass and its emit pass (one workgroup).
+void scan32(hipStream_t st, const uint32_t *in, uint64_t n, uint32_t *out) {
+    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, in, n, out);
+}
+
 int ensure_plan(Device &d, uint64_t n, uint64_t cap) {
     const uint64_t ntiles = mcrc::plan_tiles(n);
     // (one more unit record per share boundary)

@@ -1,6 +1,6 @@
 // shim_recover.h -- recover_pages, the body of crc32c_recover_pages and, with
-// `triage`, of crc32c_triage_pages (the pick and the merge are then
-// shim_triage.h's, every other launch is the same): the page
+// `triage`, of crc32c_triage_pages (the pick is then shim_triage.h's and the
+// merge takes its kind bytes, every other launch is the same): the page
 // walk and its verify (shim_walk.h), the salvage's stages behind them
 // (shim_salvage.h SalvageRun) and the merge of the two lists (k_recover.h),
 // under one lock and one lease.  A host buffer is staged once, by the walk;
@@ -78,16 +78,14 @@ int recover_stages(Device &d, hipStream_t st, const void *base, uint64_t base_by
                                    kcap};
         if (!out.offsets || !out.lens || !out.kind) return CRC32C_ENOMEM;
     }
-    if (kcap && triage) {
-        const uint64_t grid = std::min<uint64_t>((most + 1023) / 1024, 2048), per = (most + grid - 1) / grid;
-        if ((rc = triage_merge(r, a, woffs, wok, found ? &tp : nullptr, dim3((unsigned)grid), per, out))) return rc;
-    } else if (kcap) {
+    if (kcap) {
         // a workgroup per 1024 entries or more (four rounds of its threads: k_recover.h), 2048 workgroups at the most
         const uint64_t grid = std::min<uint64_t>((most + 1023) / 1024, 2048), per = (most + grid - 1) / grid;
+        // (tp.kind: the picked entries' kinds, nullptr unless the triage picked: all of them are kind 4 then)
         hipLaunchKernelGGL(mcrc_dev::k_recover_merge, dim3((unsigned)grid), dim3(256), 0, st, a,
                            (const uint64_t *)woffs, (const uint8_t *)wok, wo.prefix, nw, (const uint64_t *)found,
-                           found ? (const uint32_t *)r.ppre : (const uint32_t *)nullptr, (const uint64_t *)r.cand,
-                           (const uint32_t *)r.cand_nt, r.nc, per, out);
+                           (const uint8_t *)tp.kind, found ? (const uint32_t *)r.ppre : (const uint32_t *)nullptr,
+                           (const uint64_t *)r.cand, (const uint32_t *)r.cand_nt, r.nc, per, out);
         HIP_OK(hipGetLastError());
     }
     HIP_OK(hipStreamSynchronize(st));

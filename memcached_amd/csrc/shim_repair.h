@@ -71,8 +71,8 @@ int item_stages(Device &d, hipStream_t st, const mcrc_dev::SpanArgs &a, uint64_t
     const unsigned grid = (unsigned)mcrc::count_grid(n);
     HIP_OK(hipMemsetAsync(r.ctr, 0, mcrc_dev::kRpWords * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(mcrc_dev::k_repair_count, dim3(grid), dim3(256), 0, st, a, r);
-    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)r.lcnt, n, lpre);
-    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)r.ccnt, n, cpre);
+    scan32(st, r.lcnt, n, lpre);
+    scan32(st, r.ccnt, n, cpre);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(h, r.ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(h32, lpre + n, 4, hipMemcpyDeviceToHost, st));

@@ -76,7 +76,7 @@ struct SalvageRun {
             hipLaunchKernelGGL(mcrc_dev::k_salvage_check, dim3(mcrc::final_grid(s.nwalked)), dim3(256), 0, st, s,
                                a.base_bytes);
         launch_regions<false>(pcnt, nullptr, nullptr, 0);
-        hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)pcnt, s.nw, ppre);
+        scan32(st, pcnt, s.nw, ppre);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(h, s.ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(h32, ppre + s.nw, 4, hipMemcpyDeviceToHost, st));
@@ -100,8 +100,7 @@ struct SalvageRun {
                            (const mcrc_dev::SalvageTile *)tiles, ntiles, tcnt, (const uint32_t *)nullptr,
                            (uint64_t *)nullptr, (uint32_t *)nullptr, (uint64_t)0);
         HIP_OK(hipEventRecord(d.ev1, st));
-        hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)tcnt, (uint64_t)ntiles,
-                           tpre);
+        scan32(st, tcnt, ntiles, tpre);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(h + mcrc_dev::kSvCand, s.ctr + mcrc_dev::kSvCand, 2 * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, st));
@@ -131,15 +130,22 @@ struct SalvageRun {
         return run_items<1>(d, v, mcrc::item_route(nc, a.base_bytes, small_max()), st, &count);
     }
 
-    // out (nullptr: counted only) takes the first ocap offsets found
-    int pick(uint64_t *out, uint64_t ocap) {
+    // the count pass (cnt), the scan (into ppre) and, with out, the emit pass of
+    // one of the pick's two kinds (SUSPECTS: shim_triage.h; sus: its arrays)
+    template <bool SUSPECTS>
+    void launch_pick(uint64_t *out, uint64_t ocap, const mcrc_dev::PickSuspects &sus) {
         auto launch = [&](auto kern, uint32_t *cnt, const uint32_t *pre, uint64_t *o, uint64_t cap) {
             hipLaunchKernelGGL(kern, pgrid, pblock, 0, st, (const uint64_t *)cand, (const uint32_t *)cand_nt,
-                               (const uint8_t *)cok, nc, a.region, a.base_bytes, s.nw, cnt, pre, o, cap);
+                               (const uint8_t *)cok, nc, a.region, a.base_bytes, s.nw, cnt, pre, o, cap, sus);
         };
-        launch(mcrc_dev::k_salvage_pick<false>, pcnt, nullptr, nullptr, 0);
-        hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)pcnt, s.nw, ppre);
-        if (out) launch(mcrc_dev::k_salvage_pick<true>, nullptr, ppre, out, ocap);
+        launch(mcrc_dev::k_salvage_pick<false, SUSPECTS>, pcnt, nullptr, nullptr, 0);
+        scan32(st, pcnt, s.nw, ppre);
+        if (out) launch(mcrc_dev::k_salvage_pick<true, SUSPECTS>, nullptr, ppre, out, ocap);
+    }
+
+    // out (nullptr: counted only) takes the first ocap offsets found
+    int pick(uint64_t *out, uint64_t ocap) {
+        launch_pick<false>(out, ocap, mcrc_dev::PickSuspects{nullptr, nullptr, nullptr, nullptr});
         HIP_OK(hipGetLastError());
         return CRC32C_OK;
     }

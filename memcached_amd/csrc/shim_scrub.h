@@ -18,12 +18,12 @@
 // CRC32C_SCRUB_GAPS (opts->mode): after each triage the gap starts are counted
 // once (one count, 4 B, crosses the link); where there are any, they are
 // emitted and merged with the triage's list into a second list, and both
-// repair lists of that T are built from it (the headers' by
-// k_scrub_headers_gaps).  With none, or with the bit clear, the launches are
-// the ones above (with the bit set, one count launch, one scan and one 4 B
-// copy more per triage).  Scratch (grow-only): 12 B per gap entry (offset and
-// length; the kind is written by the merge), and 14 B per entry of the second
-// list (offset, length and a kind array per repair stage).
+// repair lists of that T are built from it, by the same two kernels.  With
+// none, or with the bit clear, the launches are the ones above (with the bit
+// set, one count launch, one scan and one 4 B copy more per triage).  Scratch
+// (grow-only): 12 B per gap entry (offset and length; the kind is written by
+// the merge), and 14 B per entry of the second list (offset, length and a kind
+// array per repair stage).
 #pragma once
 
 namespace {
@@ -67,7 +67,7 @@ struct ScrubRun {
         const dim3 grid(mcrc::walk_grid(nw)), block(64 * mcrc_dev::kWalkWaves);
         hipLaunchKernelGGL(mcrc_dev::k_scrub_gaps<false>, grid, block, 0, st, a, l, nw, cnt, (const uint32_t *)nullptr,
                            mcrc_dev::RecoverOut{nullptr, nullptr, nullptr, 0});
-        hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw, pre);
+        scan32(st, cnt, nw, pre);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(h32, pre + nw, 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -107,17 +107,15 @@ struct ScrubRun {
             hipLaunchKernelGGL(kern, grid, block, 0, st, l, wbuf_bytes, base_bytes, nw, c, p, out, cap);
         };
         using namespace mcrc_dev;
-        const auto count = ITEMS ? k_scrub_items<false> : g ? k_scrub_headers_gaps<false> : k_scrub_headers<false>;
-        const auto emit = ITEMS ? k_scrub_items<true> : g ? k_scrub_headers_gaps<true> : k_scrub_headers<true>;
-        launch(count, cnt, nullptr, nullptr, 0);
-        hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw, pre);
+        launch(ITEMS ? k_scrub_items<false> : k_scrub_headers<false>, cnt, nullptr, nullptr, 0);
+        scan32(st, cnt, nw, pre);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(h32, pre + nw, 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         *n = *h32;
         if (*n == 0) return CRC32C_OK;
         if (!(list = d.sc_list.reserve(*n * 8))) return CRC32C_ENOMEM;
-        launch(emit, nullptr, pre, list, *n);
+        launch(ITEMS ? k_scrub_items<true> : k_scrub_headers<true>, nullptr, pre, list, *n);
         HIP_OK(hipGetLastError());
         return CRC32C_OK;
     }

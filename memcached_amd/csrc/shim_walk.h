@@ -31,7 +31,7 @@ int walk_count(Device &d, hipStream_t st, const void *base, uint64_t base_bytes,
     HIP_OK(hipMemsetAsync(cnt + nw, 0, 4, st));
     hipLaunchKernelGGL(mcrc_dev::k_walk<false>, dim3(mcrc::walk_grid(nw)), dim3(64 * mcrc_dev::kWalkWaves), 0, st, *a,
                        nw, wo);
-    hipLaunchKernelGGL(mcrc_dev::k_scan32, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, nw + 1, prefix);
+    scan32(st, cnt, nw + 1, prefix);
     HIP_OK(hipMemcpyAsync(total, prefix + nw, 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return CRC32C_OK;
