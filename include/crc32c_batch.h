@@ -143,7 +143,9 @@ extern "C" {
  * at a fixed stride that overruns base_bytes is rejected up front
  * (CRC32C_EINVAL).  offsets / lens / crc_in / out hold n entries each.
  * Spans may come in any order and may overlap (chunked-item iov lists keep
- * their chain order; host batches are staged in offset order internally). */
+ * their chain order; host batches are staged in offset order internally).
+ * base needs no alignment, here and in every other call: a view into the
+ * middle of a larger allocation gives the results its bytes give anywhere. */
 typedef struct crc32c_spans {
     const void *base;
     uint64_t base_bytes;
@@ -212,6 +214,9 @@ int crc32c_batch_chains(const crc32c_spans *iovs, const uint64_t *chain_first, u
  * (storage.c:950-1070: items packed from the read's start, nkey == 0 ends it,
  * next item at + ITEM_ntotal, stop when < 48 bytes remain) and every item
  * verified as crc32c_verify_items does (with region_bytes = wbuf_bytes).
+ * base needs no alignment, and the wbuf_bytes pieces are counted from base
+ * (piece w is [base + w * wbuf_bytes, + wbuf_bytes)), in this and in every
+ * other page call (salvage, recover, triage, scrub, stamp).
  * *nitems = items found; the first min(cap, *nitems) offsets and ok flags are
  * written to offsets[] / ok[], in walk order, and *nbad counts every bad item.
  * cap == 0 is a count-only query: the walk runs, nothing is verified, *nbad =

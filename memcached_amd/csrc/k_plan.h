@@ -73,7 +73,10 @@ __device__ __forceinline__ void count_item(const SpanArgs &a, uint64_t i, const 
 // its span (M_{Ea - end}, x^(8 n) from the xpow table), XORed into the span's
 // slot (LDS, wave-private).  The chunks cover the pieces [ph, ceil16(E)) only
 // (the rest of [ph, Ea) is zeros), the piece holding E cleared from E on.
-// tests/test_count_whole_model.py restates it.
+// ph, e and ea are offsets from gb, which must be a 16-byte aligned address:
+// ceil16 of such an offset is ceil16 of the address (k_count passes base
+// rounded down, not base).  tests/test_count_whole_model.py restates it, with
+// the base's residue.
 constexpr uint32_t kCountThreads = 256;
 // (128-B chunks: half the x^(8n) multiplies of 64-B ones, mixed pages -0.6 %;
 // 256-B chunks' longer lane chains were slower: k_count_chunk_size_ab.txt)
@@ -145,7 +148,12 @@ __global__ __launch_bounds__(kCountThreads) void k_count(SpanArgs a, uint64_t *n
     // the batch: the workgroups past it leave before copying 20 KiB of tables)
     if ((uint64_t)blockIdx.x * blockDim.x >= n) return;
     const Tab8 t8 = load_tab8(s8, a.tab8);
-    gbyte *const gb = (gbyte *)a.base;
+    // whole_chunks rounds its offsets to pieces, and pieces are 16-byte
+    // aligned addresses: it gets offsets from gb = base rounded down to a
+    // piece boundary (base itself needs no alignment), so that rounding an
+    // offset rounds the address.
+    const uint64_t ba = (uintptr_t)a.base & 15u;
+    gbyte *const gb = (gbyte *)((uintptr_t)a.base - ba);
     uint32_t *const slot = wslot[threadIdx.x >> 6];
     const uint64_t lane = threadIdx.x & 63u;
     // (a wave-uniform loop: every lane takes part in whole_chunks)
@@ -156,7 +164,7 @@ __global__ __launch_bounds__(kCountThreads) void k_count(SpanArgs a, uint64_t *n
         ItemDesc it{a.base, 0u, 0u, false};
         if (valid) it = fetch_item<MODE>(a, i);
         const uint32_t t = grid_pad(it.p, it.len);
-        const uint64_t kh = (uintptr_t)it.p & 15u, off = (uint64_t)(it.p - a.base);
+        const uint64_t kh = (uintptr_t)it.p & 15u, off = (uint64_t)(it.p - a.base) + ba;  // (from gb)
         const SpanHead h = span_head(it.p, it.len);
         const bool whole = valid && it.sane && it.len != 0 && h.drop && h.g1o == (uint64_t)it.len + t;
         const uint32_t r = whole_chunks(gb, whole, off - kh, off + it.len, off + it.len + t, t8, a.xpow, slot);
@@ -522,7 +530,8 @@ __global__ void k_final(SpanArgs a, const uint4 *irec) {
             p = a.base + (sane ? off : 0);
             len = a.len;
             const SpanHead h = span_head(p, len);
-            R = sane && !(h.drop && h.g1o == len + grid_pad(p, len)) ? a.out[i] : 0u;  // (else not given to k_spans)
+            // (a span of no bytes or all its thread's is not given to k_spans: out[i] still holds the caller's word)
+            R = sane && len != 0 && !(h.drop && h.g1o == len + grid_pad(p, len)) ? a.out[i] : 0u;
             if (sane) z = span_corr(p, len, a.crc_in ? a.crc_in[i] : 0u, t8, a.xpow);
         }
         if (MODE == 1) {

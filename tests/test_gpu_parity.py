@@ -1195,7 +1195,8 @@ def test_page_stream_unsorted_offsets_bad_headers_and_tail(torch):
 def test_fuzz_spans(torch, seed):
     """Seeded fuzz of crc32c_batch: random (possibly overlapping) offsets, a
     mix of tiny, ~4 KiB, multi-block and multi-segment lengths, random crc_in
-    or none, random base misalignment; compared with the oracle."""
+    or none, random base misalignment (seeds 4..7: the buffer is a view that
+    starts 1..15 bytes into its allocation); compared with the oracle."""
     rng = np.random.default_rng(1000 + seed)
     n = int(rng.integers(1, 1500))
     kind = rng.integers(0, 4, n)
@@ -1208,7 +1209,9 @@ def test_fuzz_spans(torch, seed):
     offs = np.array([rng.integers(0, size - int(l) + 1) for l in lens], dtype=np.uint64)
     cin = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32) if seed % 2 else None
     want = oracle.batch(host, offs, lens, cin)
-    d = _dev(torch, host)
+    shift = int(np.random.default_rng(3000 + seed).integers(1, 16)) if seed >= 4 else 0  # (rng's own draws stay as they were)
+    d = _dev(torch, np.concatenate([np.full(shift, 0xA5, np.uint8), host]))[shift:]
+    assert d.data_ptr() % 16 == shift and d.numel() == host.size
     out = mc.batch(d, offsets=_dev(torch, offs.view(np.int64)), lens=_dev(torch, lens.view(np.int32)),
                    crc_in=None if cin is None else _dev(torch, cin.view(np.int32)))
     torch.cuda.synchronize()
