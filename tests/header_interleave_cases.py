@@ -5,7 +5,6 @@ rule's model (tests/header_model.py).  No GPU and no library call to build
 them; tests/test_gpu_interleave_headers.py runs them among that table's ops and
 tests/test_header_interleave_cases.py checks that the two tables together
 reach every batch entry point of include/crc32c_batch.h."""
-import ctypes
 import functools
 
 import numpy as np
@@ -13,6 +12,7 @@ import numpy as np
 from . import header_cases as hc
 from . import header_model as hm
 from . import interleave_cases as ic
+from . import raw_calls
 from . import salvage_cases as sc
 from .repair_cases import flip, place
 
@@ -20,22 +20,9 @@ ENTRY = "crc32c_repair_headers"
 
 
 def _call_headers(op, side):
-    from memcached_amd import _lib
     i = op.inputs
-    buf, offs = side.data(i["buf"]), side.desc(i["offsets"])
-    n = i["offsets"].size
-    ok, bit, lens = side.out(n, np.uint8), side.out(n, np.uint64), side.out(n, np.uint32)
-    nrep, nbad = ctypes.c_uint64(ic.SENT64), ctypes.c_uint64(ic.SENT64)
-    rc = _lib.lib.crc32c_repair_headers(ic.ptr(buf), i["buf"].size, 0, ic.ptr(offs), n, ic.ptr(ok), ic.ptr(bit),
-                                        ic.ptr(lens), ctypes.byref(nrep), ctypes.byref(nbad),
-                                        side.flags | i["flags"], side.handle)
-    ok, bit, lens = side.host(ok, np.uint8), side.host(bit, np.uint64), side.host(lens, np.uint32)
-    got = {"rc": rc, "nrepaired": nrep.value, "nbad": nbad.value, "buf": side.host(buf, np.uint8)}
-    if "ok" in op.want:
-        got.update(ok=ok, bit=bit, lens=lens)
-    else:  # (unspecified after CRC32C_EWORK; the words behind them are not)
-        got.update(ok_end=int(ok[n]), bit_end=int(bit[n]), lens_end=int(lens[n]))
-    return got
+    got = raw_calls.repair_headers(side, i["buf"], i["offsets"], locate_only=bool(i["flags"] & ic.LOCATE_ONLY))
+    return ic._stated(op, got, i["offsets"].size)
 
 
 @functools.lru_cache(maxsize=None)

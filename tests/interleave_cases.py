@@ -7,8 +7,8 @@ models under tests/ alone.  Inputs and expectations are built once per process.
 
 Every output array an op hands to the library has one more entry than the call
 may write, filled with a sentinel; run() returns the arrays whole and the
-expected arrays end with the sentinel."""
-import contextlib
+expected arrays end with the sentinel.  Side, the sentinels and the callers of
+the page-recovery entry points are tests/raw_calls.py's."""
 import ctypes
 import functools
 from dataclasses import dataclass, field
@@ -19,104 +19,19 @@ from . import chain_cases as cc
 from . import copy_cases
 from . import copy_items_model
 from . import oracle
+from . import raw_calls
 from . import recover_model
 from . import repair_cases
 from . import repair_model
 from . import routes_cases as rc_
 from . import salvage_cases as sc
 from . import salvage_model as sm
+from .raw_calls import (ASYNC, DEVICE, EINVAL, ERANGE, EWORK, KEEP_STAMPED, LOCATE_ONLY, OK,  # noqa: F401
+                        RECOVER_COUNTS, SENT, SENT64, _capped, _lib, _ro, ended, ptr)
 
-OK, EINVAL, ERANGE, EWORK = 0, -3, -5, -7
-DEVICE, ASYNC, KEEP_STAMPED, LOCATE_ONLY = 0x1, 0x2, 0x10, 0x20
-SENT64 = 0x5A5A5A5A5A5A5A5A
-SENT = {1: SENT64 & 0xFF, 4: SENT64 & 0xFFFFFFFF, 8: SENT64}
 MiB = 1 << 20
-
-
-def _lib():
-    from memcached_amd import _lib as m  # (loads libmcrc32c.so: only run() gets here)
-    return m
-
-
-def _ro(a):
-    a.setflags(write=False)
-    return a
-
-
-def ended(a, dtype=None):
-    """An expected output array: a, and the sentinel behind its end."""
-    a = np.asarray(a, dtype)
-    return _ro(np.concatenate((a, np.array([SENT[a.itemsize]], a.dtype))))
-
-
-class Side:
-    """Where one run's copies live -- "device" (torch tensors made and read on
-    `stream`, or on the default stream), "host" (pageable numpy arrays) or
-    "pinned" (the data buffers in crc32c_host_alloc memory) -- and the flag and
-    the stream handle that go with it."""
-
-    def __init__(self, torch, stream, where):
-        self.torch, self.stream, self.where = torch, stream, where
-        self.dev = where == "device"
-        self.flags = DEVICE if self.dev else 0
-        self.handle = None
-        self._pins, self._ctx = [], contextlib.nullcontext()
-        if self.dev:
-            self._ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-            self.handle = ctypes.c_void_p((torch.cuda.default_stream() if stream is None else stream).cuda_stream)
-
-    def __enter__(self):
-        self._ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        for p in self._pins:
-            _lib().lib.crc32c_host_free(p)
-        return self._ctx.__exit__(*exc)
-
-    def _tensor(self, a):
-        signed = {"uint64": np.int64, "uint32": np.int32}.get(a.dtype.name)
-        return self.torch.from_numpy(np.array(a.view(signed) if signed else a)).cuda()
-
-    def data(self, a):
-        """A fresh, writable copy of a data buffer."""
-        if self.dev:
-            return self._tensor(a)
-        if self.where == "pinned":
-            p = _lib().lib.crc32c_host_alloc(max(a.size, 1))
-            assert p, "crc32c_host_alloc failed"
-            self._pins.append(p)
-            arr = np.ctypeslib.as_array((ctypes.c_uint8 * a.size).from_address(p))
-            arr[:] = a
-            return arr
-        return a.copy()
-
-    def desc(self, a):
-        """A fresh copy of a descriptor array (None stays None)."""
-        if a is None:
-            return None
-        return self._tensor(a) if self.dev else a.copy()
-
-    def out(self, n, dtype):
-        """An output array of n entries and the sentinel's, all holding it."""
-        dtype = np.dtype(dtype)
-        if self.dev:
-            t = {1: self.torch.uint8, 4: self.torch.int32, 8: self.torch.int64}[dtype.itemsize]
-            return self.torch.full((n + 1,), SENT[dtype.itemsize], dtype=t, device="cuda")
-        return np.full(n + 1, SENT[dtype.itemsize], dtype)
-
-    def host(self, x, dtype):
-        """What an array of this run holds now, as numpy (the run's stream is
-        waited for)."""
-        if self.dev:
-            return x.cpu().numpy().view(dtype)
-        return np.array(x).view(dtype)
-
-
-def ptr(x):
-    if x is None:
-        return None
-    return x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data
+# (the tables' arrays end with one sentinel word, not raw_calls.EXTRA)
+Side = functools.partial(raw_calls.Side, pad=1)
 
 
 def _u64(v=SENT64):
@@ -179,7 +94,7 @@ def _call_spans(op, side):
     if op.entry == "crc32c_batch_multi":
         rc = _lib().lib.crc32c_batch_multi(ctypes.byref(s), 1)
     else:
-        rc = _lib().lib.crc32c_batch(ctypes.byref(s), side.flags, side.handle)
+        rc = _lib().lib.crc32c_batch(ctypes.byref(s), side.flags(), side.handle)
     return {"rc": rc, "out": side.host(out, np.uint32)}
 
 
@@ -259,7 +174,7 @@ def _call_chains(op, side):
     iov_out, out = side.out(i["n"], np.uint32), side.out(i["nchains"], np.uint32)
     s = spans_struct(side, op, buf, iov_out)
     first = side.desc(i["first"])
-    rc = _lib().lib.crc32c_batch_chains(ctypes.byref(s), ptr(first), i["nchains"], ptr(out), side.flags, side.handle)
+    rc = _lib().lib.crc32c_batch_chains(ctypes.byref(s), ptr(first), i["nchains"], ptr(out), side.flags(), side.handle)
     return {"rc": rc, "iov_out": side.host(iov_out, np.uint32), "out": side.host(out, np.uint32)}
 
 
@@ -289,7 +204,7 @@ def _call_items(op, side):
     n = i["offsets"].size
     ok, nbad = side.out(n, np.uint8), _u64()
     fn = getattr(_lib().lib, op.entry)
-    rc = fn(ptr(buf), i["buf"].size, 0, ptr(offs), n, ptr(ok), ctypes.byref(nbad), side.flags | i["flags"],
+    rc = fn(ptr(buf), i["buf"].size, 0, ptr(offs), n, ptr(ok), ctypes.byref(nbad), side.flags() | i["flags"],
             side.handle)
     got = {"rc": rc, "ok": side.host(ok, np.uint8), "nbad": nbad.value}
     if "buf" in op.want:
@@ -333,20 +248,12 @@ def _call_pages(op, side):
     nitems, nbad = _u64(), _u64()
     fn = getattr(_lib().lib, op.entry)
     rc = fn(ptr(buf), i["buf"].size, i["wbuf"], ptr(offs), ptr(ok), cap, ctypes.byref(nitems), ctypes.byref(nbad),
-            side.flags | i["flags"], side.handle)
+            side.flags() | i["flags"], side.handle)
     got = {"rc": rc, "offsets": side.host(offs, np.uint64), "ok": side.host(ok, np.uint8), "nitems": nitems.value,
            "nbad": nbad.value}
     if "buf" in op.want:
         got["buf"] = side.host(buf, np.uint8)
     return got
-
-
-def _capped(values, cap, dtype):
-    """An output array of cap entries that received min(cap, len) values."""
-    a = np.full(cap, SENT[np.dtype(dtype).itemsize], dtype)
-    k = min(cap, len(values))
-    a[:k] = values[:k]
-    return ended(a)
 
 
 def _page_ops():
@@ -374,17 +281,17 @@ def _page_ops():
 
 # -- salvage and recover ---------------------------------------------------------
 
+def _stated(op, got, n=None):
+    """The part of a raw caller's result that the op states: its "buf" is the
+    call's "after", and behind CRC32C_EWORK only the word behind each array's n entries."""
+    got = dict(got, buf=got["after"])
+    got.update((key, int(got[key[:-4]][n])) for key in op.want if key.endswith("_end"))
+    return {key: got[key] for key in op.want}
+
+
 def _call_salvage(op, side):
     i = op.inputs
-    buf = side.data(i["buf"])
-    walked, wok = side.desc(i["walked"]), side.desc(i["walked_ok"])
-    offs = side.out(i["cap"], np.uint64)
-    nf, ns, nc = _u64(), _u64(), _u64()
-    rc = _lib().lib.crc32c_salvage_pages(ptr(buf), i["buf"].size, i["wbuf"], ptr(walked), ptr(wok), i["walked"].size,
-                                         ptr(offs), i["cap"], ctypes.byref(nf), ctypes.byref(ns), ctypes.byref(nc),
-                                         side.flags, side.handle)
-    return {"rc": rc, "offsets": side.host(offs, np.uint64), "nfound": nf.value, "scanned": ns.value,
-            "ncand": nc.value}
+    return _stated(op, raw_calls.salvage_pages(side, i["buf"], i["wbuf"], i["walked"], i["walked_ok"], cap=i["cap"]))
 
 
 def _salvage_op(name, where, buf, W, walked=None, wok=None, refused=False):
@@ -405,21 +312,9 @@ def _salvage_op(name, where, buf, W, walked=None, wok=None, refused=False):
               demand=buf.size // 128 + (0 if where == "device" else buf.size), kind="salvage")
 
 
-RECOVER_COUNTS = ("nitems", "nbad", "nsalvaged", "scanned", "ncand")
-
-
 def _call_recover(op, side):
     i = op.inputs
-    buf = side.data(i["buf"])
-    cap = i["cap"]
-    offs, lens, kind = side.out(cap, np.uint64), side.out(cap, np.uint32), side.out(cap, np.uint8)
-    counts = [_u64() for _ in RECOVER_COUNTS]
-    rc = _lib().lib.crc32c_recover_pages(ptr(buf), i["buf"].size, i["wbuf"], ptr(offs), ptr(lens), ptr(kind), cap,
-                                         *map(ctypes.byref, counts), side.flags, side.handle)
-    got = {"rc": rc, "offsets": side.host(offs, np.uint64), "lens": side.host(lens, np.uint32),
-           "kind": side.host(kind, np.uint8)}
-    got.update(zip(RECOVER_COUNTS, (c.value for c in counts)))
-    return got
+    return _stated(op, raw_calls.listed_pages(op.entry, side, i["buf"], i["wbuf"], cap=i["cap"]))
 
 
 def _recover_op(name, where, buf, W):
@@ -458,19 +353,9 @@ def _salvage_ops():
 
 def _call_repair(op, side):
     i = op.inputs
-    buf, offs = side.data(i["buf"]), side.desc(i["offsets"])
-    n = i["offsets"].size
-    ok, bit = side.out(n, np.uint8), side.out(n, np.uint64)
-    nrep, nbad = _u64(), _u64()
-    rc = _lib().lib.crc32c_repair_items(ptr(buf), i["buf"].size, 0, ptr(offs), n, i["max_span"], ptr(ok), ptr(bit),
-                                        ctypes.byref(nrep), ctypes.byref(nbad), side.flags | i["flags"], side.handle)
-    ok, bit = side.host(ok, np.uint8), side.host(bit, np.uint64)
-    got = {"rc": rc, "nrepaired": nrep.value, "buf": side.host(buf, np.uint8)}
-    if "ok" in op.want:
-        got.update(ok=ok, bit=bit, nbad=nbad.value)
-    else:  # (unspecified after CRC32C_EWORK; the words behind them are not)
-        got.update(ok_end=int(ok[n]), bit_end=int(bit[n]))
-    return got
+    got = raw_calls.repair_items(side, i["buf"], i["offsets"], max_span=i["max_span"],
+                                 locate_only=bool(i["flags"] & LOCATE_ONLY))
+    return _stated(op, got, i["offsets"].size)
 
 
 def _repair_ops():
@@ -509,7 +394,7 @@ def _call_copy(op, side):
     n = i["src_offsets"].size
     ok, nbad = side.out(n, np.uint8), _u64()
     rc = _lib().lib.crc32c_copy_items(ptr(src), i["src"].size, i["wbuf"], ptr(so), ptr(dst), i["dst_init"].size, ptr(do),
-                                      n, ptr(ok), ctypes.byref(nbad), side.flags, side.handle)
+                                      n, ptr(ok), ctypes.byref(nbad), side.flags(), side.handle)
     return {"rc": rc, "ok": side.host(ok, np.uint8), "nbad": nbad.value, "dst": side.host(dst, np.uint8),
             "src": side.host(src, np.uint8)}
 

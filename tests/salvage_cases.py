@@ -107,6 +107,13 @@ def hand_built():
     return buf, K16
 
 
+# the cases of small_cases() that the GPU tests of every page-recovery call run by name
+SMALL = ["hdr_" + k for k in HEADER_DAMAGE] + [
+    "data_only", "first_image", "last_image", "two_adjacent", "header_then_data", "ends_exact", "ends_one_short",
+    "lookalike_in_intact", "lookalike_in_damaged", "no_crlf", "cflags64", "cflags64_read_as_32", "config5_small",
+    "ranges_6", "ranges_over_64"]
+
+
 def small_cases():
     """name -> (buf, W, cfl): every case small enough for the byte-by-byte model."""
     out = {}

@@ -5,42 +5,24 @@ it, each count, the return code, the page afterwards) from the rule's model
 library call to build them; tests/test_gpu_interleave_scrub.py runs them among
 that table's ops, and tests/test_scrub_interleave_cases.py checks that every
 entry point taking a crc32c_scrub_opts is an entry here."""
-import ctypes
 import functools
 
-import numpy as np
-
 from . import interleave_cases as ic
+from . import raw_calls
+from .raw_calls import _capped
 from . import scrub_cases as sca
 from . import scrub_model as scm
 
 ENTRY = "crc32c_scrub_pages"
-WORDS = scm.COUNTS + ("nflips", "headers_repaired", "items_repaired", "rounds", "complete")
-LISTS = (("offsets", np.uint64), ("lens", np.uint32), ("kind", np.uint8), ("flip_offsets", np.uint64),
-         ("flip_bits", np.uint64), ("flip_by", np.uint8))
+WORDS, LISTS = raw_calls.SCRUB_WORDS, raw_calls.SCRUB_LISTS
+assert WORDS[:6] == scm.COUNTS
 
 
 def _call_scrub(op, side):
-    from memcached_amd import _lib
     i = op.inputs
-    buf = side.data(i["buf"])
-    rooms = [i["cap"]] * 3 + [i["flip_cap"]] * 3
-    arrays = [side.out(room, dtype) for room, (_, dtype) in zip(rooms, LISTS)]
-    ptrs = [ic.ptr(a) for a in arrays]
-    opts = _lib.ScrubOpts(side.flags | i["mode"], 0, i["max_rounds"], side.handle)
-    out = _lib.ScrubOut(*ptrs[:3], i["cap"], *ptrs[3:], i["flip_cap"], *([ic.SENT64] * 9), ic.SENT[4], ic.SENT[4])
-    rc = _lib.lib.crc32c_scrub_pages(ic.ptr(buf), i["buf"].size, i["wbuf"], ctypes.byref(opts), ctypes.byref(out))
-    got = {"rc": rc, "buf": side.host(buf, np.uint8)}
-    got.update((name, side.host(a, dtype)) for a, (name, dtype) in zip(arrays, LISTS))
-    got.update((w, int(getattr(out, w))) for w in WORDS)
-    return got
-
-
-def _capped(values, cap, dtype):
-    a = np.full(cap, ic.SENT[np.dtype(dtype).itemsize], dtype)
-    k = min(cap, len(values))
-    a[:k] = values[:k]
-    return ic.ended(a)
+    got = raw_calls.scrub_pages(side, i["buf"], i["wbuf"], cap=i["cap"], flip_cap=i["flip_cap"],
+                                max_rounds=i["max_rounds"], locate_only=bool(i["mode"] & ic.LOCATE_ONLY))
+    return ic._stated(op, got)
 
 
 def _op(name, where, case, short=0, mode=0, max_rounds=0, refused=False):

@@ -17,7 +17,9 @@ caller's out[] word for a kernel's result when a fixed-length batch of
 zero-length spans went past the single-launch route, at every shift and at
 none (test_chains' zeros_fixed_len0, test_batch_shared_length's length 0:
 out[] is pre-filled here)."""
+import contextlib
 import ctypes
+import types
 
 import numpy as np
 import pytest
@@ -37,6 +39,7 @@ from . import copy_items_model
 from . import header_model as hm
 from . import keep_stamped_model as ks
 from . import oracle
+from . import raw_calls as raw
 from . import recover_model
 from . import repair_bytes_model as bm
 from . import repair_model as rm
@@ -47,39 +50,29 @@ from . import scrub_gaps_cases as gc
 from . import scrub_gaps_model as gm
 from . import scrub_model as scm
 from . import triage_model as tm
-from .test_gpu_recover import _call as recover_call
-from .test_gpu_recover import _expect as recover_expect
-from .test_gpu_salvage import SMALL as SALVAGE_NAMES
-from .test_gpu_scrub import DTYPES, EXTRA, LISTS, SENT, SENT8, SENT32, WORDS
-from .test_gpu_scrub import check as scrub_check
-from .test_gpu_triage import _call as triage_call
-from .test_gpu_triage import _expect as triage_expect
+from .salvage_cases import SMALL as SALVAGE_NAMES
 
 pytestmark = pytest.mark.gpu
 SLACK = bs.SLACK
+LISTS, WORDS = [name for name, _ in raw.SCRUB_LISTS], raw.SCRUB_WORDS
 
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw.need_gpu()
 
 
 @pytest.fixture(params=["small", "planned"])
 def route(request):
     """Both span routes, as test_gpu_parity.py's fixture sets them."""
-    prev = _lib.lib.crc32c_set_small_max(0 if request.param == "planned" else 8192)
-    yield request.param
-    _lib.lib.crc32c_set_small_max(prev)
+    with raw.small_max(0 if request.param == "planned" else 8192):
+        yield request.param
 
 
 @pytest.fixture
 def planned():
-    prev = _lib.lib.crc32c_set_small_max(0)
-    yield "planned"
-    _lib.lib.crc32c_set_small_max(prev)
+    with raw.small_max(0):
+        yield "planned"
 
 
 # ---------------------------------------------------------------------------
@@ -104,24 +97,16 @@ def _holds(alloc, B, s):
                              f"(view byte {int(at[0]) - SLACK - s} of {len(B)})")
 
 
-class _Pinned:
-    """A crc32c_host_alloc allocation holding B framed at s; .view is what the library gets."""
-
-    def __init__(self, B, s):
-        framed = bs.frame(B, s)
-        self.p = _lib.lib.crc32c_host_alloc(framed.size)
-        assert self.p and self.p % 256 == 0
-        self.arr = np.ctypeslib.as_array((ctypes.c_uint8 * framed.size).from_address(self.p))
-        self.arr[:] = framed
-        self.view = self.arr[SLACK + s:SLACK + s + B.size]
-        assert self.view.ctypes.data == self.p + SLACK + s
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.arr = self.view = None
-        _lib.lib.crc32c_host_free(self.p)
+@contextlib.contextmanager
+def _Pinned(B, s):
+    """A crc32c_host_alloc allocation (.arr) holding B framed at s; .view is what the library gets."""
+    framed = bs.frame(B, s)
+    with raw.pinned(framed.size) as arr:
+        assert arr.ctypes.data % 256 == 0
+        arr[:] = framed
+        view = arr[SLACK + s:SLACK + s + B.size]
+        assert view.ctypes.data == arr.ctypes.data + SLACK + s
+        yield types.SimpleNamespace(arr=arr, view=view)
 
 
 def _d(torch, a, view):
@@ -263,13 +248,9 @@ def test_chains(torch, route, name, s):
         sp = _lib.Spans(v.data_ptr(), case.buf.size, None if doffs is None else doffs.data_ptr(), case.stride,
                         None if dlens is None else dlens.data_ptr(), case.length, None, iov_out.data_ptr(), case.n)
         # (the case's own route, and the planned path)
-        prev = mc.set_small_max(case.small_max) if route == "small" and case.small_max is not None else None
-        try:
+        with raw.small_max(case.small_max if route == "small" else None):
             rc = _lib.lib.crc32c_batch_chains(ctypes.byref(sp), dfirst.data_ptr(), case.nchains, out.data_ptr(),
                                               _lib.CRC32C_DEVICE, torch.cuda.current_stream().cuda_stream)
-        finally:
-            if prev is not None:
-                mc.set_small_max(prev)
         assert rc == _lib.CRC32C_OK
         torch.cuda.synchronize()
         _holds(alloc, case.buf, s)
@@ -426,18 +407,14 @@ def test_copy_items(torch, route, ss, ds):
 def test_copy_items_page_locked(route, ss, ds):
     """Both buffers page-locked: read and written in place by the GPU."""
     dst_init, (w_dst, w_ok, w_bad, w_erange) = _copy_want()
-    pins = []
-
-    def place(B, sh):
-        pins.append(_Pinned(B, sh))
-        return pins[-1].arr, pins[-1].view
 
     def run(s):
-        try:
+        with contextlib.ExitStack() as pins:
+            def place(B, sh):
+                pin = pins.enter_context(_Pinned(B, sh))
+                return pin.arr, pin.view
+
             return _copy_run(place, lambda a: a, *(s or (0, 0)))
-        finally:
-            while pins:
-                pins.pop().__exit__()
 
     _both(("copy_pinned", route), run, (ss, ds), (w_ok, w_bad))
 
@@ -576,9 +553,13 @@ def test_salvage_pages(torch, planned, name, s):
         _both(("salvage", name, with_lists), run, s, m[with_lists])
 
 
-def _listed(got):
-    rc, offs, lens, kind, counts = got
-    return rc, offs, lens, kind, tuple(sorted(counts.items()))
+def _listed(entry, torch, v, buf, W, cfl, m, tag):
+    """One recover or triage call over the placed view v against the model: (rc, the arrays whole, the counts)."""
+    cap = m["nitems"] + 3
+    got = raw.listed_pages(entry, raw.Side(torch).adopt(v), buf, W, cap=cap, cfl=cfl)
+    raw.expect_unchanged(got, buf)
+    raw.expect_listed(got, cap, m, raw.COUNTS[entry], tag=tag)
+    return (got["rc"],) + tuple(got[name] for name, _ in raw.LISTED) + tuple(got[k] for k in raw.COUNTS[entry])
 
 
 @pytest.mark.parametrize("s", bs.THIN)
@@ -586,14 +567,12 @@ def _listed(got):
 def test_recover_pages(torch, planned, name, s):
     buf, W, cfl = _salvage_case(name)
     m = _page_model("recover", name)
-    cap = m["nitems"] + 3
     got = {}
     for sh in (0, s):
         alloc, v = _place(torch, buf, sh)
-        got[sh] = recover_call(buf, W, cap, True, cfl == 8, dbuf=v)  # (checks the view unchanged)
+        got[sh] = _listed("crc32c_recover_pages", torch, v, buf, W, cfl, m, sh)
         _holds(alloc, buf, sh)
-        recover_expect(got[sh], cap, m["rc"], m["offsets"], m["lens"], m["kind"], m, sh)
-    _same(_listed(got[s]), _listed(got[0]), f"recover {name}: shift {s} against shift 0")
+    _same(got[s], got[0], f"recover {name}: shift {s} against shift 0")
 
 
 @pytest.mark.parametrize("s", bs.THIN)
@@ -601,34 +580,12 @@ def test_recover_pages(torch, planned, name, s):
 def test_triage_pages(torch, planned, name, s):
     buf, W, cfl = _salvage_case(name)
     m = _page_model("triage", name)
-    cap = m["nitems"] + 3
     got = {}
     for sh in (0, s):
         alloc, v = _place(torch, buf, sh)
-        got[sh] = triage_call(buf, W, cap, True, cfl == 8, dbuf=v)
+        got[sh] = _listed("crc32c_triage_pages", torch, v, buf, W, cfl, m, sh)
         _holds(alloc, buf, sh)
-        triage_expect(got[sh], cap, m, sh)
-    _same(_listed(got[s]), _listed(got[0]), f"triage {name}: shift {s} against shift 0")
-
-
-def _scrub(torch, v, nbytes, W, cap, flip_cap, cfl, max_span=0, max_rounds=0, gaps=False):
-    """One crc32c_scrub_pages over the device view v, the six arrays with EXTRA
-    sentinel words behind their room (tests/test_gpu_scrub.py's call, with the
-    mode bit and the caller's buffer)."""
-    mode = _lib.CRC32C_DEVICE | (_lib.CRC32C_CFLAGS64 if cfl == 8 else 0) | (_lib.CRC32C_SCRUB_GAPS if gaps else 0)
-    rooms = (cap, cap, cap, flip_cap, flip_cap, flip_cap)
-    sents = (SENT, SENT32, SENT8, SENT, SENT, SENT8)
-    types = (torch.int64, torch.int32, torch.uint8, torch.int64, torch.int64, torch.uint8)
-    arrays = [torch.full((n + EXTRA,), x, dtype=t, device="cuda") for n, x, t in zip(rooms, sents, types)]
-    ptrs = [a.data_ptr() for a in arrays]
-    opts = _lib.ScrubOpts(mode, max_span, max_rounds, torch.cuda.current_stream().cuda_stream)
-    out = _lib.ScrubOut(*ptrs[:3], cap, *ptrs[3:], flip_cap, *([SENT] * 9), SENT32, SENT32)
-    rc = _lib.lib.crc32c_scrub_pages(v.data_ptr(), nbytes, W, ctypes.byref(opts), ctypes.byref(out))
-    torch.cuda.synchronize()
-    got = {w: int(getattr(out, w)) for w in WORDS}
-    got.update(rc=rc, raw=dict(zip(LISTS, [a.cpu().numpy().astype(d) for a, d in zip(arrays, DTYPES)])),
-               after=v.cpu().numpy(), rooms=dict(zip(LISTS, rooms)))
-    return got
+    _same(got[s], got[0], f"triage {name}: shift {s} against shift 0")
 
 
 # (cases module, name, CRC32C_SCRUB_GAPS): scrub_cases' pages and scrub_gaps_cases' with their own arguments,
@@ -658,13 +615,14 @@ def test_scrub_pages(torch, planned, cases, name, gaps, s):
     got = {}
     for sh in (0, s):
         alloc, v = _place(torch, buf, sh)
-        got[sh] = _scrub(torch, v, buf.size, W, m["nitems"], m["nflips"], cfl, gaps=on, **kw)
-        scrub_check(got[sh], m)
+        got[sh] = raw.scrub_pages(raw.Side(torch).adopt(v), buf, W, cap=m["nitems"], flip_cap=m["nflips"], cfl=cfl,
+                                  gaps=on, **kw)
+        raw.expect_scrub(got[sh], m)
         _holds(alloc, m["after"], sh)
     a, b = got[s], got[0]
     assert {w: a[w] for w in WORDS + ("rc",)} == {w: b[w] for w in WORDS + ("rc",)}
     for n in LISTS:
-        np.testing.assert_array_equal(a["raw"][n], b["raw"][n], err_msg=n)
+        np.testing.assert_array_equal(a[n], b[n], err_msg=n)
 
 
 # ---------------------------------------------------------------------------
@@ -677,10 +635,9 @@ def test_two_queued_jobs_over_one_page_locked_buffer(route):
     buf, offs, lens, cin, _, _, perm = bs.batch_parts()[0]
     rng = np.random.default_rng(1900)
     X = rng.integers(1, 256, 129 + buf.size + SLACK, dtype=np.uint8)
-    p = _lib.lib.crc32c_host_alloc(X.size)
-    assert p and p % 256 == 0
-    try:
-        arr = np.ctypeslib.as_array((ctypes.c_uint8 * X.size).from_address(p))
+    with raw.pinned(X.size) as arr:
+        p = arr.ctypes.data
+        assert p % 256 == 0
         arr[:] = X
         jobs = []
         for base in (1, 129):
@@ -695,6 +652,3 @@ def test_two_queued_jobs_over_one_page_locked_buffer(route):
         for base, job, out, sp, o, n in jobs:
             np.testing.assert_array_equal(out, oracle.batch(X[base:base + buf.size], o, n, cin), err_msg=f"base + {base}")
         np.testing.assert_array_equal(arr, X)
-    finally:
-        arr = None
-        _lib.lib.crc32c_host_free(p)

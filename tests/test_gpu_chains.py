@@ -5,7 +5,6 @@ chains, the fold's length digits, more chains than k_chain has threads, a
 caller's stream, and the return codes.  Device path, and host path over
 pageable and page-locked buffers.  Bit-exact against the oracle
 (chain_cases.expected_chains, itself checked by tests/test_chain_model.py)."""
-import contextlib
 import ctypes
 import time
 
@@ -18,9 +17,9 @@ except ImportError:
     pass
 
 from memcached_amd import _lib
-from memcached_amd import crc32c as mc
 
 from . import chain_cases as cc
+from . import raw_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -30,22 +29,7 @@ WHERE = ("device", "host", "pinned")
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
-
-
-@contextlib.contextmanager
-def _small_max(value):
-    if value is None:
-        yield
-        return
-    prev = mc.set_small_max(value)
-    try:
-        yield
-    finally:
-        mc.set_small_max(prev)
+    return raw_calls.need_gpu()
 
 
 _want = {}
@@ -103,7 +87,7 @@ def _run(torch, case, where, *, base_bytes=None, first=None, nchains=None, crc_i
     keep += [buf, offs, lens, dfirst, cin]
     sp = _lib.Spans(_ptr(buf), base_bytes, _ptr(offs), case.stride, _ptr(lens), case.length, _ptr(cin),
                     _ptr(iov_out), n)
-    with _small_max(case.small_max):
+    with raw_calls.small_max(case.small_max):
         rc = _lib.lib.crc32c_batch_chains(ctypes.byref(sp), None if null_first else _ptr(dfirst), nchains,
                                           None if null_out else _ptr(out), flags, stream)
     if where == "device":
@@ -197,7 +181,7 @@ def test_async_on_a_callers_stream(torch):
             out = torch.full((case.nchains,), SENT, dtype=torch.int32, device="cuda")
             sp = _lib.Spans(buf.data_ptr(), case.buf.size, offs.data_ptr(), 0, lens.data_ptr(), case.length, None,
                             iov_out.data_ptr(), case.n)
-            with _small_max(case.small_max):
+            with raw_calls.small_max(case.small_max):
                 rc = _lib.lib.crc32c_batch_chains(ctypes.byref(sp), first.data_ptr(), case.nchains, out.data_ptr(),
                                                   _lib.CRC32C_DEVICE | _lib.CRC32C_ASYNC,
                                                   ctypes.c_void_p(st.cuda_stream))

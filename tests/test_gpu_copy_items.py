@@ -19,6 +19,7 @@ from memcached_amd import _lib, layout
 from memcached_amd import crc32c as mc
 
 from . import copy_items_model as model
+from . import raw_calls
 from .copy_cases import WBUF, mixed_case
 from .copy_cases import stamp_all as _stamp_all
 
@@ -29,10 +30,7 @@ ROUTES = ["device", "pinned", "pageable"]
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 def _dev(torch, arr):

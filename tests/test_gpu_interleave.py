@@ -7,7 +7,6 @@ the CPU models expect.  All calls of a process share the Device's grow-only
 scratch and hand it from stream to stream; nothing expected here comes from the
 library."""
 import collections
-import contextlib
 import ctypes
 import threading
 
@@ -26,6 +25,7 @@ from . import copy_items_model
 from . import interleave_cases as ic
 from . import keep_stamped_model as ks
 from . import oracle
+from . import raw_calls
 from . import routes_cases
 
 pytestmark = pytest.mark.gpu
@@ -36,28 +36,13 @@ ASYNC = _lib.CRC32C_DEVICE | _lib.CRC32C_ASYNC
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
-
-
-@contextlib.contextmanager
-def _small_max(value):
-    if value is None:
-        yield
-        return
-    prev = mc.set_small_max(value)
-    try:
-        yield
-    finally:
-        mc.set_small_max(prev)
+    return raw_calls.need_gpu()
 
 
 def _run_and_check(torch, op, stream=None, tag="", tune=True):
     """tune: the chain ops that name a route below the small-batch limit get
     it through crc32c_set_small_max, which is process-wide: one thread only."""
-    with _small_max(op.small_max if tune else None):
+    with raw_calls.small_max(op.small_max if tune else None):
         got = op.run(torch, stream)
     ic.check(op, got, tag)
 

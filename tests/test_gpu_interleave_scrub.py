@@ -13,9 +13,8 @@ try:  # GPU processes load torch (and its HIP runtime) before libmcrc32c.so
 except ImportError:
     pass
 
-from memcached_amd import crc32c as mc
-
 from . import interleave_cases as ic
+from . import raw_calls
 from . import scrub_interleave_cases as sic
 
 pytestmark = pytest.mark.gpu
@@ -26,19 +25,12 @@ GOOD_OPS = [op for op in SCRUB_OPS if not op.error]
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 def _run_and_check(torch, op, tag=""):
-    prev = mc.set_small_max(op.small_max) if op.small_max is not None else None
-    try:
+    with raw_calls.small_max(op.small_max):
         got = op.run(torch, None)
-    finally:
-        if prev is not None:
-            mc.set_small_max(prev)
     ic.check(op, got, tag)
 
 

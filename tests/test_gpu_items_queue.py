@@ -20,16 +20,14 @@ from memcached_amd import _lib, layout, shard
 from memcached_amd import crc32c as mc
 
 from . import oracle
+from . import raw_calls
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 @pytest.fixture(params=["small", "planned"])

@@ -19,6 +19,7 @@ from memcached_amd import crc32c as mc
 
 from . import keep_stamped_model as model
 from . import oracle
+from . import raw_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +36,7 @@ def span_path(request):
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 def _dev(torch, arr):

@@ -22,6 +22,7 @@ from . import chain_cases as cc
 from . import copy_items_model as cm
 from . import keep_stamped_model as ks
 from . import oracle
+from . import raw_calls
 from . import salvage_cases as sc
 from . import salvage_model as sm
 
@@ -33,10 +34,7 @@ FLIPPED = 4
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 @pytest.fixture(scope="module")

@@ -18,6 +18,7 @@ from memcached_amd import _lib
 from memcached_amd import crc32c as mc
 
 from . import oracle
+from . import raw_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +29,7 @@ SPAN_MAX = 256 << 10      # kQueueSpanMax
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 @pytest.fixture(scope="module")

@@ -11,58 +11,29 @@ import pytest
 
 from memcached_amd import _lib
 from memcached_amd import crc32c as mc
+from tests import raw_calls as raw
 from tests import recover_model as rm
 from tests import salvage_cases as sc
-from tests.test_gpu_salvage import SMALL
+from tests.salvage_cases import SMALL
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5A5A5A5A5A5A5A5A
-SENT32, SENT8 = SENT & 0xFFFFFFFF, SENT & 0xFF
-COUNTS = ("nitems", "nbad", "nsalvaged", "scanned", "ncand")
+ENTRY = "crc32c_recover_pages"
+COUNTS = raw.RECOVER_COUNTS
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _flags(dev, cflags64):
-    return (_lib.CRC32C_CFLAGS64 if cflags64 else 0) | (_lib.CRC32C_DEVICE if dev else 0)
-
-
-def _call(buf, W, cap, dev, cflags64=False, null_arrays=False, dbuf=None):
-    """One library call over buf (host) or its device copy (dbuf: one the
-    caller placed).  Returns (rc, offsets, lens, kind -- cap + 4 words each,
-    pre-filled with the sentinel -- and the five counts); checks that the
-    buffer is unchanged."""
-    counts = [ctypes.c_uint64(SENT) for _ in range(5)]
-    refs = [ctypes.byref(c) for c in counts]
-    if dev:
-        torch = _torch()
-        if dbuf is None:
-            dbuf = torch.from_numpy(buf).cuda()
-        out = [torch.full((cap + 4,), s, dtype=t, device="cuda")
-               for s, t in ((SENT, torch.int64), (SENT32, torch.int32), (SENT8, torch.uint8))]
-        ptrs = [None] * 3 if null_arrays else [o.data_ptr() for o in out]
-        rc = _lib.lib.crc32c_recover_pages(dbuf.data_ptr(), buf.size, W, *ptrs, cap, *refs, _flags(True, cflags64),
-                                           torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        assert torch.equal(dbuf.cpu(), torch.from_numpy(buf)), "base was written"
-        got = [o.cpu().numpy().astype(d) for o, d in zip(out, (np.uint64, np.uint32, np.uint8))]
-    else:
-        keep = buf.copy()
-        got = [np.full(cap + 4, s, d) for s, d in ((SENT, np.uint64), (SENT32, np.uint32), (SENT8, np.uint8))]
-        ptrs = [None] * 3 if null_arrays else [g.ctypes.data for g in got]
-        rc = _lib.lib.crc32c_recover_pages(buf.ctypes.data, buf.size, W, *ptrs, cap, *refs, _flags(False, cflags64),
-                                           None)
-        assert np.array_equal(buf, keep), "base was written"
-    return (rc, *got, dict(zip(COUNTS, (c.value for c in counts))))
+def _call(buf, W, cap, dev, cfl=4, null_arrays=False, side=None):
+    """One call over a copy of buf on one route (side: one that holds a buffer
+    the caller placed); the buffer is unchanged."""
+    got = raw.listed_pages(ENTRY, dev if side is None else side, buf, W, cap=cap, cfl=cfl,
+                           null_arrays=null_arrays)
+    raw.expect_unchanged(got, buf)
+    return got
 
 
 def _two_calls(buf, W, dev, cflags64=False):
     """The same answer from crc32c_verify_pages followed by crc32c_salvage_pages
     (offsets and kinds merged here; the lengths are the model's alone)."""
-    src = _torch().from_numpy(buf).cuda() if dev else buf
+    src = raw.need_gpu().from_numpy(buf).cuda() if dev else buf
     walked, wok, nbad = mc.verify_pages(src, W, cflags64=cflags64)
     rc = _lib.CRC32C_OK
     try:
@@ -75,20 +46,8 @@ def _two_calls(buf, W, dev, cflags64=False):
     offs = np.concatenate((walked, found))
     kind = np.concatenate((wok, np.full(found.size, _lib.CRC32C_ITEM_SALVAGED, np.uint8)))
     order = np.argsort(offs, kind="stable")
-    counts = dict(nitems=offs.size, nbad=nbad, nsalvaged=found.size, **info)
-    return rc, offs[order].tolist(), kind[order].tolist(), counts
-
-
-def _expect(got, cap, rc, offs, lens, kind, counts, tag):
-    """One call's results against one expected answer, cut at cap."""
-    grc, goffs, glens, gkind, gcounts = got
-    assert grc == rc, tag
-    assert gcounts == {k: counts[k] for k in COUNTS}, tag
-    k = min(cap, len(offs))
-    assert goffs[:k].tolist() == offs[:k] and gkind[:k].tolist() == kind[:k], tag
-    if lens is not None:
-        assert glens[:k].tolist() == lens[:k], tag
-    assert (goffs[k:] == SENT).all() and (glens[k:] == SENT32).all() and (gkind[k:] == SENT8).all(), tag
+    return dict(rc=rc, offsets=offs[order].tolist(), kind=kind[order].tolist(), nitems=offs.size, nbad=nbad,
+                nsalvaged=found.size, **info)
 
 
 def _check(buf, W, cfl=4, small=(None, 0), routes=(True, False), model=None):
@@ -96,18 +55,13 @@ def _check(buf, W, cfl=4, small=(None, 0), routes=(True, False), model=None):
     cf64 = cfl == 8
     m = model or rm.recover(buf, W, cfl)
     for sm_max in small:
-        prev = mc.set_small_max(sm_max) if sm_max is not None else None
-        try:
+        with raw.small_max(sm_max):
             for dev in routes:
                 tag = (sm_max, dev)
                 cap = m["nitems"] + 3
-                got = _call(buf, W, cap, dev, cf64)
-                _expect(got, cap, m["rc"], m["offsets"], m["lens"], m["kind"], m, tag)
-                rc2, offs2, kind2, counts2 = _two_calls(buf, W, dev, cf64)
-                _expect(got, cap, rc2, offs2, None, kind2, counts2, tag)
-        finally:
-            if prev is not None:
-                mc.set_small_max(prev)
+                got = _call(buf, W, cap, dev, cfl)
+                raw.expect_listed(got, cap, m, COUNTS, tag=tag)
+                raw.expect_listed(got, cap, _two_calls(buf, W, dev, cf64), COUNTS, lens=False, tag=tag)
     return m
 
 
@@ -146,9 +100,9 @@ def test_caps(cases):
     assert n >= 3 and m["nsalvaged"] >= 1
     for dev in (True, False):
         for cap in (1, n - 1, n):
-            _expect(_call(buf, W, cap, dev), cap, m["rc"], m["offsets"], m["lens"], m["kind"], m, (dev, cap))
+            raw.expect_listed(_call(buf, W, cap, dev), cap, m, COUNTS, tag=(dev, cap))
         # cap == 0: everything is still computed, the arrays may be NULL
-        _expect(_call(buf, W, 0, dev, null_arrays=True), 0, m["rc"], [], [], [], m, (dev, 0))
+        raw.expect_listed(_call(buf, W, 0, dev, null_arrays=True), 0, m, COUNTS, tag=(dev, 0))
     # scanned and ncand may be NULL
     c = [ctypes.c_uint64(0) for _ in range(3)]
     rc = _lib.lib.crc32c_recover_pages(buf.ctypes.data, buf.size, W, None, None, None, 0, *map(ctypes.byref, c), None,
@@ -168,26 +122,22 @@ def test_a_device_buffer_off_the_tile_grid(cases):
     """base + 4096 + 23: off the scan's 4 KiB tiles and off every 16-byte boundary."""
     buf, W, cfl = cases["many_found"]
     m = rm.recover(buf, W, cfl)
-    torch = _torch()
+    torch = raw.need_gpu()
     pad = 4096 + 23
     dbig = torch.zeros(pad + buf.size, dtype=torch.uint8, device="cuda")
     dbig[pad:] = torch.from_numpy(buf).cuda()
     cap = m["nitems"] + 3
-    _expect(_call(buf, W, cap, True, dbuf=dbig[pad:]), cap, m["rc"], m["offsets"], m["lens"], m["kind"], m, "off grid")
+    raw.expect_listed(_call(buf, W, cap, True, side=raw.Side(torch).adopt(dbig[pad:])), cap, m, COUNTS, tag="off grid")
 
 
 def test_a_page_locked_host_buffer(cases):
     buf, W, cfl = cases["hdr_cas_bit"]
     m = rm.recover(buf, W, cfl)
-    p = _lib.lib.crc32c_host_alloc(buf.size)
-    assert p
-    try:
-        pinned = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (buf.size,))
+    with raw.pinned(buf.size) as pinned:
         pinned[:] = buf
         cap = m["nitems"] + 3
-        _expect(_call(pinned, W, cap, False), cap, m["rc"], m["offsets"], m["lens"], m["kind"], m, "pinned")
-    finally:
-        _lib.lib.crc32c_host_free(p)
+        got = _call(buf, W, cap, False, side=raw.Side(where="host").adopt(pinned))
+        raw.expect_listed(got, cap, m, COUNTS, tag="pinned")
 
 
 def test_config5_shape_goes_through_the_k5_verify_route():
@@ -206,7 +156,7 @@ def test_python_face_numpy_and_torch(cases):
     offs, lens, kind, got = mc.recover_pages(buf, W)
     assert (offs.dtype, lens.dtype, kind.dtype) == (np.uint64, np.uint32, np.uint8)
     assert (offs.tolist(), lens.tolist(), kind.tolist(), got) == (m["offsets"], m["lens"], m["kind"], info)
-    torch = _torch()
+    torch = raw.need_gpu()
     offs, lens, kind, got = mc.recover_pages(torch.from_numpy(buf).cuda(), W)
     assert offs.is_cuda and lens.is_cuda and kind.is_cuda
     assert (offs.cpu().tolist(), lens.cpu().tolist(), kind.cpu().tolist(), got) == (m["offsets"], m["lens"], m["kind"],

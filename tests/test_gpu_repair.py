@@ -2,13 +2,12 @@
 afterwards are compared exactly with the rule's model (tests/repair_model.py),
 for device tensors and host arrays, with crc32c_set_small_max at its default
 and at 0 (k_small and the planned path compute the CRCs)."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from memcached_amd import _lib
 from memcached_amd import crc32c as mc
+from tests import raw_calls as raw
 from tests import repair_model as rm
 from tests import salvage_cases as sc
 from tests.repair_cases import flip as _flip
@@ -19,23 +18,12 @@ pytestmark = pytest.mark.gpu
 NO_BIT, REPAIRED = rm.NO_BIT, rm.REPAIRED
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def _run(buf, offs, dev, **kw):
     """mc.repair_items over a copy of buf: (ok, bit, info, the copy afterwards)."""
-    offs = np.asarray(offs, np.uint64)
-    if dev:
-        torch = _torch()
-        t = torch.from_numpy(buf.copy()).cuda()
-        ok, bit, info = mc.repair_items(t, torch.from_numpy(offs.astype(np.int64)).cuda(), **kw)
-        torch.cuda.synchronize()
-        return ok.cpu().numpy(), bit.cpu().numpy().view(np.uint64), info, t.cpu().numpy()
-    b = buf.copy()
-    ok, bit, info = mc.repair_items(b, offs, **kw)
-    return ok, bit, info, b
+    side = raw.Side(where=dev)
+    page = side.data(buf)
+    ok, bit, info = mc.repair_items(page, side.desc(np.asarray(offs, np.uint64)), **kw)
+    return side.host(ok, np.uint8), side.host(bit, np.uint64), info, side.host(page, np.uint8)
 
 
 def _check(buf, offs, small=(None,), region=0, cfl=4, max_span=0, locate_only=False, verify=True):
@@ -43,8 +31,7 @@ def _check(buf, offs, small=(None,), region=0, cfl=4, max_span=0, locate_only=Fa
     offs = np.asarray(offs, np.uint64)
     ok, bit, nrep, nbad, after = rm.repair(buf, offs, region, cfl, max_span, locate_only)
     for sm_max in small:
-        prev = mc.set_small_max(sm_max) if sm_max is not None else None
-        try:
+        with raw.small_max(sm_max):
             for dev in (True, False):
                 tag = (sm_max, dev)
                 gok, gbit, info, gafter = _run(buf, offs, dev, region_bytes=region, max_span=max_span,
@@ -57,9 +44,6 @@ def _check(buf, offs, small=(None,), region=0, cfl=4, max_span=0, locate_only=Fa
                     vok, vbad = mc.verify_items(gafter, offs, region_bytes=region, cflags64=cfl == 8)
                     assert (np.asarray(vok) != 0).tolist() == (ok != 0).tolist(), tag
                     assert vbad == nbad, tag
-        finally:
-            if prev is not None:
-                mc.set_small_max(prev)
     return ok, bit
 
 
@@ -172,16 +156,7 @@ def test_locate_only_leaves_the_buffer_alone():
     assert ok.tolist() == b[0].tolist() and info["nrepaired"] == b[2]
 
 
-def _raw(buf_ptr, nbytes, offs_ptr, n, ok_ptr, bit_ptr, flags, max_span=0, nrep=True, nbad=True, stream=None):
-    r, b = ctypes.c_uint64(77), ctypes.c_uint64(77)
-    rc = _lib.lib.crc32c_repair_items(buf_ptr, nbytes, 0, offs_ptr, n, max_span, ok_ptr, bit_ptr,
-                                      ctypes.byref(r) if nrep else None, ctypes.byref(b) if nbad else None, flags,
-                                      stream)
-    return rc, r.value, b.value
-
-
 def test_bounds_and_arguments():
-    torch = _torch()
     rng = np.random.default_rng(6)
     nt = 100000
     img = sc.image_nt(rng, nt)
@@ -189,36 +164,25 @@ def test_bounds_and_arguments():
     _flip(buf, int(offs[1]), 8 * 5000 + 2)
     assert 3 * (nt - 32) > buf.size > 2 * (nt - 32)
     three = np.array([offs[1]] * 3 + [offs[0]], np.uint64)
-    ok, bit = np.zeros(8, np.uint8), np.zeros(8, np.uint64)
     for dev in (False, True):
-        keep = buf.copy()
-        if dev:
-            d = [torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x).cuda() for x in (keep, three, ok, bit)]
-            p = [t.data_ptr() for t in d]
-            flags, st = _lib.CRC32C_DEVICE, torch.cuda.current_stream().cuda_stream
-        else:
-            p = [x.ctypes.data for x in (keep, three, ok, bit)]
-            flags, st = 0, None
-        unchanged = (lambda: torch.equal(d[0].cpu(), torch.from_numpy(buf))) if dev else (
-            lambda: np.array_equal(keep, buf))
         # the spans of the one image named three times pass base_bytes
-        rc, nrep, _ = _raw(p[0], buf.size, p[1], 4, p[2], p[3], flags, stream=st)
-        assert rc == _lib.CRC32C_EWORK and nrep == 0 and unchanged()
+        got = raw.repair_items(dev, buf, three)
+        assert (got["rc"], got["nrepaired"]) == (_lib.CRC32C_EWORK, 0)
+        raw.expect_unchanged(got, buf)
         # twice stays below it: the call works (that image's content is unspecified; the other is intact)
-        rc, _, _ = _raw(p[0], buf.size, p[1] + 8, 3, p[2], p[3], flags | _lib.CRC32C_LOCATE_ONLY, stream=st)
-        assert rc == _lib.CRC32C_OK and unchanged()
+        got = raw.repair_items(dev, buf, three[1:], locate_only=True)
+        assert got["rc"] == _lib.CRC32C_OK
+        raw.expect_unchanged(got, buf)
         # n == 0
-        assert _raw(p[0], buf.size, p[1], 0, p[2], p[3], flags, stream=st) == (_lib.CRC32C_OK, 0, 0)
+        got = raw.repair_items(dev, buf, three, n=0)
+        assert (got["rc"], got["nrepaired"], got["nbad"]) == (_lib.CRC32C_OK, 0, 0)
         # each NULL argument, max_span over the limit
-        for i in range(4):
-            q = list(p)
-            q[i] = None
-            assert _raw(q[0], buf.size, q[1], 4, q[2], q[3], flags, stream=st)[0] == _lib.CRC32C_EINVAL
-        assert _raw(p[0], buf.size, p[1], 4, p[2], p[3], flags, nrep=False, stream=st)[0] == _lib.CRC32C_EINVAL
-        assert _raw(p[0], buf.size, p[1], 4, p[2], p[3], flags, nbad=False, stream=st)[0] == _lib.CRC32C_EINVAL
-        assert _raw(p[0], buf.size, p[1], 4, p[2], p[3], flags, max_span=_lib.CRC32C_REPAIR_SPAN_MAX + 1,
-                    stream=st)[0] == _lib.CRC32C_EINVAL
-        assert unchanged()
+        refused = [raw.repair_items(dev, buf, three, null=(name,))
+                   for name in ("buf", "offsets", "ok", "bit", "nrepaired", "nbad")]
+        refused.append(raw.repair_items(dev, buf, three, max_span=_lib.CRC32C_REPAIR_SPAN_MAX + 1))
+        for got in refused:
+            assert got["rc"] == _lib.CRC32C_EINVAL
+            raw.expect_unchanged(got, buf)
     with pytest.raises(mc.Crc32cError) as e:
         mc.repair_items(buf.copy(), three)
     assert e.value.rc == _lib.CRC32C_EWORK
@@ -234,14 +198,14 @@ def test_the_flow_behind_recover_pages(name):
         buf = buf.copy()
         _flip(buf, W + 4165 * 5, 8 * 2000 + 6)
     for dev in (True, False):
-        src = _torch().from_numpy(buf.copy()).cuda() if dev else buf.copy()
+        src = raw.need_gpu().from_numpy(buf.copy()).cuda() if dev else buf.copy()
         offs, lens, kind, info = mc.recover_pages(src, W, cflags64=cfl == 8)
         host = (lambda x: x.cpu().numpy()) if dev else np.asarray
         sel = (host(kind) == 0) & (host(lens) != 0)
         bad = host(offs).astype(np.uint64)[sel]
         assert bad.size >= 1
         want = rm.repair(buf, bad, W, cfl)
-        todo = _torch().from_numpy(bad.astype(np.int64)).cuda() if dev else bad
+        todo = raw.need_gpu().from_numpy(bad.astype(np.int64)).cuda() if dev else bad
         ok, bit, rinfo = mc.repair_items(src, todo, region_bytes=W, cflags64=cfl == 8)
         assert host(ok).tolist() == want[0].tolist() and host(bit).view(np.uint64).tolist() == want[1].tolist()
         assert rinfo == {"nrepaired": want[2], "nbad": want[3]} and want[2] >= 1

@@ -2,14 +2,13 @@
 buffer afterwards are compared exactly with the rule's model
 (tests/repair_bytes_model.py), for device tensors and pageable host arrays, and
 every image the call repaired then passes verify_items."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from memcached_amd import _lib
 from memcached_amd import crc32c as mc
 from tests import repair_bytes_cases as bc
+from tests import raw_calls as raw
 from tests import repair_bytes_model as bm
 from tests import repair_cases as rc
 from tests import repair_model as rm
@@ -21,23 +20,13 @@ pytestmark = pytest.mark.gpu
 NO_BIT, REPAIRED = bm.NO_BIT, bm.REPAIRED
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def _run(buf, offs, dev, **kw):
     """mc.repair_bytes over a copy of buf: (ok, byte, mask, info, the copy afterwards)."""
-    offs = np.asarray(offs, np.uint64)
-    if dev:
-        torch = _torch()
-        t = torch.from_numpy(buf.copy()).cuda()
-        ok, byte, mask, info = mc.repair_bytes(t, torch.from_numpy(offs.astype(np.int64)).cuda(), **kw)
-        torch.cuda.synchronize()
-        return ok.cpu().numpy(), byte.cpu().numpy().view(np.uint64), mask.cpu().numpy(), info, t.cpu().numpy()
-    b = buf.copy()
-    ok, byte, mask, info = mc.repair_bytes(b, offs, **kw)
-    return ok, byte, mask, info, b
+    side = raw.Side(where=dev)
+    page = side.data(buf)
+    ok, byte, mask, info = mc.repair_bytes(page, side.desc(np.asarray(offs, np.uint64)), **kw)
+    return (side.host(ok, np.uint8), side.host(byte, np.uint64), side.host(mask, np.uint8), info,
+            side.host(page, np.uint8))
 
 
 def _check(buf, offs, region=0, cfl=4, max_span=0, locate_only=False, routes=(True, False)):
@@ -168,8 +157,8 @@ def test_superset_of_the_one_bit_call():
     buf, offs, kinds = rc.mixed(rng, 2000, 3000)
     ok, byte, mask = _check(buf, offs, max_span=3000)
     for dev in (True, False):
-        src = _torch().from_numpy(buf).cuda() if dev else buf
-        todo = _torch().from_numpy(offs.astype(np.int64)).cuda() if dev else offs
+        src = raw.need_gpu().from_numpy(buf).cuda() if dev else buf
+        todo = raw.need_gpu().from_numpy(offs.astype(np.int64)).cuda() if dev else offs
         iok, ibit, _ = mc.repair_items(src, todo, max_span=3000, locate_only=True)
         if dev:
             iok, ibit = iok.cpu().numpy(), ibit.cpu().numpy().view(np.uint64)
@@ -217,53 +206,41 @@ def test_locate_only_leaves_the_buffer_alone():
     assert ok.tolist() == b[0].tolist() and mask.tolist() == b[2].tolist() and info["nrepaired"] == b[3]
 
 
-def _raw(ptrs, nbytes, n, mode, stream, max_span=0):
-    opts = _lib.BytesOpts(mode, max_span, stream)
-    out = _lib.BytesOut(ptrs[2], ptrs[3], ptrs[4], 77, 77)
-    rc_ = _lib.lib.crc32c_repair_bytes(ptrs[0], nbytes, 0, ptrs[1], n, ctypes.byref(opts), ctypes.byref(out))
-    return rc_, out.nrepaired, out.nbad
-
-
 def test_bounds_and_arguments():
-    torch = _torch()
     rng = np.random.default_rng(80)
     nt = 100000
     buf, offs = rc.place([sc.image_nt(rng, 300), sc.image_nt(rng, nt), sc.image_nt(rng, 120000), sc.image_nt(rng, 300)])
     bc.xor_byte(buf, int(offs[1]), 5000, 0x66)
     assert 3 * (nt - 32) > buf.size > 2 * (nt - 32)
     three = np.array([offs[1]] * 3 + [offs[0]], np.uint64)
-    ok, byte, mask = np.zeros(8, np.uint8), np.zeros(8, np.uint64), np.zeros(8, np.uint8)
     span = bm.SPAN_MAX
+    OK, EINVAL, UNSET = _lib.CRC32C_OK, _lib.CRC32C_EINVAL, raw.SENT64  # (UNSET: a count word the call left alone)
+    words = lambda got: (got["rc"], got["nrepaired"], got["nbad"])  # noqa: E731
     for dev in (False, True):
-        keep = buf.copy()
-        if dev:
-            d = [torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x).cuda()
-                 for x in (keep, three, ok, byte, mask)]
-            p = [t.data_ptr() for t in d]
-            mode, st = _lib.CRC32C_DEVICE, torch.cuda.current_stream().cuda_stream
-        else:
-            p = [x.ctypes.data for x in (keep, three, ok, byte, mask)]
-            mode, st = 0, None
-        unchanged = (lambda: torch.equal(d[0].cpu(), torch.from_numpy(buf))) if dev else (
-            lambda: np.array_equal(keep, buf))
         # the spans of the one image named three times pass base_bytes
-        assert _raw(p, buf.size, 4, mode, st, span) == (_lib.CRC32C_EWORK, 0, 0) and unchanged()
+        got = raw.repair_bytes(dev, buf, three, max_span=span)
+        assert words(got) == (_lib.CRC32C_EWORK, 0, 0)
+        raw.expect_unchanged(got, buf)
         # twice stays below it: the call works
-        q = [p[0], p[1] + 8] + p[2:]
-        assert _raw(q, buf.size, 3, mode | _lib.CRC32C_LOCATE_ONLY, st, span)[0] == _lib.CRC32C_OK and unchanged()
+        got = raw.repair_bytes(dev, buf, three[1:], max_span=span, locate_only=True)
+        assert got["rc"] == OK
+        raw.expect_unchanged(got, buf)
         # n == 0
-        assert _raw(p, buf.size, 0, mode, st, span) == (_lib.CRC32C_OK, 0, 0)
+        assert words(raw.repair_bytes(dev, buf, three, n=0, max_span=span)) == (OK, 0, 0)
         # each NULL argument, max_span over the limit
-        for i in range(5):
-            q = list(p)
-            q[i] = None
-            assert _raw(q, buf.size, 4, mode, st, span) == (_lib.CRC32C_EINVAL, 77, 77)
-        assert _lib.lib.crc32c_repair_bytes(p[0], buf.size, 0, p[1], 4, None, None) == _lib.CRC32C_EINVAL
-        assert _raw(p, buf.size, 4, mode, st, span + 1) == (_lib.CRC32C_EINVAL, 77, 77)
+        refused = [raw.repair_bytes(dev, buf, three, max_span=span, null=(name,))
+                   for name in ("buf", "offsets", "ok", "byte", "mask")]
+        refused.append(raw.repair_bytes(dev, buf, three, max_span=span + 1))
+        for got in refused:
+            assert words(got) == (EINVAL, UNSET, UNSET)
+            raw.expect_unchanged(got, buf)
+        side = raw.Side(where=dev)
+        page, lst = side.data(buf), side.desc(three)
+        assert _lib.lib.crc32c_repair_bytes(raw.ptr(page), buf.size, 0, raw.ptr(lst), 4, None, None) == EINVAL
         # flags this call does not know are ignored (CRC32C_ASYNC has no effect: the counts are there)
-        q = [p[0], p[1] + 16] + p[2:]
-        assert _raw(q, buf.size, 2, mode | _lib.CRC32C_ASYNC | _lib.CRC32C_LOCATE_ONLY, st, span) == (_lib.CRC32C_OK, 1, 0)
-        assert unchanged()
+        got = raw.repair_bytes(dev, buf, three[2:], max_span=span, asynchronous=True, locate_only=True)
+        assert words(got) == (OK, 1, 0)
+        raw.expect_unchanged(got, buf)
     with pytest.raises(mc.Crc32cError) as e:
         mc.repair_bytes(buf.copy(), three, max_span=span)
     assert e.value.rc == _lib.CRC32C_EWORK
@@ -276,24 +253,18 @@ def test_bounds_and_arguments():
 
 
 def test_a_page_locked_buffer_and_a_stream_of_its_own():
-    torch = _torch()
+    torch = raw.need_gpu()
     rng = np.random.default_rng(90)
     buf, offs, _ = bc.mixed(rng, 400, percent=25)
     want = bm.repair(buf, offs)
     assert want[3] > 60
     # page-locked host memory, repaired in place by the host route
-    ptr = _lib.lib.crc32c_host_alloc(buf.size)
-    assert ptr
-    try:
-        pinned = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), (buf.size,))
+    with raw.pinned(buf.size) as pinned:
         pinned[:] = buf
         ok, byte, mask, info = mc.repair_bytes(pinned, offs)
         assert ok.tolist() == want[0].tolist() and byte.tolist() == want[1].tolist()
         assert mask.tolist() == want[2].tolist() and info == {"nrepaired": want[3], "nbad": want[4]}
         assert np.array_equal(pinned, want[5])
-        del pinned
-    finally:
-        _lib.lib.crc32c_host_free(ptr)
     # a device buffer on a stream that is not the current one
     st = torch.cuda.Stream()
     t = torch.from_numpy(buf.copy()).cuda()
@@ -324,13 +295,13 @@ def test_the_flow_behind_triage_pages():
     want = bm.repair(buf, todo, W)
     assert want[3] >= 3 and offs[1][3] in todo.tolist()
     for dev in (True, False):
-        src = _torch().from_numpy(buf.copy()).cuda() if dev else buf.copy()
+        src = raw.need_gpu().from_numpy(buf.copy()).cuda() if dev else buf.copy()
         host = (lambda x: x.cpu().numpy()) if dev else np.asarray
         o, lens, kind, _ = mc.triage_pages(src, W)
         mine = np.array(scm.item_list(host(o).astype(np.uint64).tolist(), host(lens).tolist(), host(kind).tolist()),
                         np.uint64)
         assert mine.tolist() == todo.tolist()
-        lst = _torch().from_numpy(mine.astype(np.int64)).cuda() if dev else mine
+        lst = raw.need_gpu().from_numpy(mine.astype(np.int64)).cuda() if dev else mine
         ok, byte, mask, info = mc.repair_bytes(src, lst, region_bytes=W)
         assert host(ok).tolist() == want[0].tolist() and host(byte).view(np.uint64).tolist() == want[1].tolist()
         assert host(mask).tolist() == want[2].tolist() and info == {"nrepaired": want[3], "nbad": want[4]}

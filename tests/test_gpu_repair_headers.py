@@ -3,9 +3,6 @@ buffer afterwards are compared exactly with the rule's model
 (tests/header_model.py), for device tensors and host arrays, with
 crc32c_set_small_max at its default and at 0 (k_small and the planned path
 compute the candidates' CRCs)."""
-import contextlib
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -13,6 +10,7 @@ from memcached_amd import _lib
 from memcached_amd import crc32c as mc
 from tests import header_cases as hc
 from tests import header_model as hm
+from tests import raw_calls as raw
 from tests import salvage_cases as sc
 from tests.repair_cases import flip, place
 
@@ -20,35 +18,13 @@ pytestmark = pytest.mark.gpu
 NO_BIT, REPAIRED = hm.NO_BIT, hm.REPAIRED
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def _run(buf, offs, dev, **kw):
     """mc.repair_headers over a copy of buf: (ok, bit, lens, info, the copy afterwards)."""
-    offs = np.asarray(offs, np.uint64)
-    if dev:
-        torch = _torch()
-        t = torch.from_numpy(buf.copy()).cuda()
-        ok, bit, lens, info = mc.repair_headers(t, torch.from_numpy(offs.astype(np.int64)).cuda(), **kw)
-        torch.cuda.synchronize()
-        return (ok.cpu().numpy(), bit.cpu().numpy().view(np.uint64), lens.cpu().numpy().view(np.uint32), info,
-                t.cpu().numpy())
-    b = buf.copy()
-    ok, bit, lens, info = mc.repair_headers(b, offs, **kw)
-    return ok, bit, lens, info, b
-
-
-@contextlib.contextmanager
-def _small_max(value):
-    """crc32c_set_small_max for a block: None leaves the default (k_small), 0 sends every batch to the planned path."""
-    prev = mc.set_small_max(value) if value is not None else None
-    try:
-        yield
-    finally:
-        if prev is not None:
-            mc.set_small_max(prev)
+    side = raw.Side(where=dev)
+    page = side.data(buf)
+    ok, bit, lens, info = mc.repair_headers(page, side.desc(np.asarray(offs, np.uint64)), **kw)
+    return (side.host(ok, np.uint8), side.host(bit, np.uint64), side.host(lens, np.uint32), info,
+            side.host(page, np.uint8))
 
 
 def _check(buf, offs, small=(None, 0), region=0, cfl=4, locate_only=False):
@@ -56,8 +32,7 @@ def _check(buf, offs, small=(None, 0), region=0, cfl=4, locate_only=False):
     offs = np.asarray(offs, np.uint64)
     ok, bit, lens, nrep, nbad, after = hm.repair(buf, offs, region, cfl, locate_only)
     for sm_max in small:
-        prev = mc.set_small_max(sm_max) if sm_max is not None else None
-        try:
+        with raw.small_max(sm_max):
             for dev in (True, False):
                 tag = (sm_max, dev)
                 gok, gbit, glens, info, gafter = _run(buf, offs, dev, region_bytes=region, locate_only=locate_only,
@@ -70,9 +45,6 @@ def _check(buf, offs, small=(None, 0), region=0, cfl=4, locate_only=False):
                 if not locate_only:  # what the call accepted, and only that, now verifies
                     vok, vbad = mc.verify_items(gafter, offs, region_bytes=region, cflags64=cfl == 8)
                     assert (np.asarray(vok) != 0).tolist() == (ok != 0).tolist(), tag
-        finally:
-            if prev is not None:
-                mc.set_small_max(prev)
     return ok, bit, lens, after
 
 
@@ -125,7 +97,7 @@ def test_locate_only_leaves_the_buffer_alone():
     assert np.array_equal(a[3], buf) and int((a[0] == REPAIRED).sum()) > 400
     # a read-only host buffer is accepted so
     for sm_max in (None, 0):
-        with _small_max(sm_max):
+        with raw.small_max(sm_max):
             ok, bit, lens, info = mc.repair_headers(bytes(buf), offs, locate_only=True)
         assert ok.tolist() == b[0].tolist() and info["nrepaired"] == b[3]
 
@@ -147,7 +119,7 @@ def small_cases():
 @pytest.mark.parametrize("small", [None, 0])
 @pytest.mark.parametrize("name", sorted(FLOW))
 def test_the_flow_behind_recover_pages(name, small, small_cases):
-    with _small_max(small):
+    with raw.small_max(small):
         _flow(name, small_cases)
 
 
@@ -156,7 +128,7 @@ def _flow(name, small_cases):
     nrep, nlisted = FLOW[name]
     want = _WANT.get(name)  # (the model's verdicts: computed once per case)
     for dev in (True, False):
-        src = _torch().from_numpy(buf.copy()).cuda() if dev else buf.copy()
+        src = raw.need_gpu().from_numpy(buf.copy()).cuda() if dev else buf.copy()
         host = (lambda x: x.cpu().numpy()) if dev else np.asarray
         offs, lens, kind, info = mc.recover_pages(src, W, cflags64=cfl == 8)
         todo = hc.breaks_from(host(offs).view(np.uint64), host(lens), host(kind), buf.size, W)
@@ -164,7 +136,7 @@ def _flow(name, small_cases):
         if want is None:
             want = _WANT[name] = hm.repair(buf, todo, W, cfl)
             assert want[3] == nrep and (nlisted is None or todo.size == nlisted)
-        dtodo = _torch().from_numpy(todo.astype(np.int64)).cuda() if dev else todo
+        dtodo = raw.need_gpu().from_numpy(todo.astype(np.int64)).cuda() if dev else todo
         ok, bit, hlens, rinfo = mc.repair_headers(src, dtodo, region_bytes=W, cflags64=cfl == 8)
         assert host(ok).tolist() == want[0].tolist() and host(bit).view(np.uint64).tolist() == want[1].tolist()
         assert host(hlens).view(np.uint32).tolist() == want[2].tolist()
@@ -181,22 +153,13 @@ def _flow(name, small_cases):
                 assert again.get(o) == 1, (name, o)
 
 
-def _raw(p, nbytes, n, flags, stream=None, skip=None):
-    r, b = ctypes.c_uint64(77), ctypes.c_uint64(77)
-    args = [p[0], nbytes, 0, p[1], n, p[2], p[3], p[4], ctypes.byref(r), ctypes.byref(b), flags, stream]
-    if skip is not None:
-        args[skip] = None
-    return _lib.lib.crc32c_repair_headers(*args), r.value, b.value
-
-
 @pytest.mark.parametrize("small", [None, 0])
 def test_bounds_and_arguments(small):
-    with _small_max(small):
+    with raw.small_max(small):
         _bounds_and_arguments()
 
 
 def _bounds_and_arguments():
-    torch = _torch()
     rng = np.random.default_rng(6)
     nt = 100000
     buf, offs = place([sc.image_nt(rng, nt), sc.image_nt(rng, 110000), sc.image_nt(rng, 110000)], lead=11)
@@ -206,39 +169,31 @@ def _bounds_and_arguments():
     # past the end, the damaged header and an intact one
     many = np.full(40, offs[0], np.uint64)
     few = np.array([buf.size - 47, buf.size, buf.size + 5, offs[0], offs[1]], np.uint64)
-    lists = np.concatenate([many, few])
-    ok, bit, lens = np.full(64, 9, np.uint8), np.full(64, 9, np.uint64), np.full(64, 9, np.uint32)
+    words = lambda got: (got["rc"], got["nrepaired"], got["nbad"])  # noqa: E731
     for dev in (False, True):
-        keep = buf.copy()
-        if dev:
-            d = [torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else
-                                  x.view(np.int32) if x.dtype == np.uint32 else x).cuda()
-                 for x in (keep, lists, ok, bit, lens)]
-            p = [t.data_ptr() for t in d]
-            flags, st = _lib.CRC32C_DEVICE, torch.cuda.current_stream().cuda_stream
-        else:
-            d = [keep, lists, ok.copy(), bit.copy(), lens.copy()]
-            p = [x.ctypes.data for x in d]
-            flags, st = 0, None
-        got = (lambda i: d[i].cpu().numpy() if dev else d[i])
-        unchanged = lambda: np.array_equal(got(0), buf)  # noqa: E731
         # the spans of the one true variant named 40 times pass the bound
-        assert _raw(p, buf.size, 40, flags, st) == (_lib.CRC32C_EWORK, 0, 0) and unchanged()
+        got = raw.repair_headers(dev, buf, many)
+        assert words(got) == (_lib.CRC32C_EWORK, 0, 0)
+        raw.expect_unchanged(got, buf)
         # n == 0
-        assert _raw(p, buf.size, 0, flags, st) == (_lib.CRC32C_OK, 0, 0)
+        assert words(raw.repair_headers(dev, buf, many, n=0)) == (_lib.CRC32C_OK, 0, 0)
         assert _lib.lib.crc32c_last_kernel_ms() == 0
         # each NULL argument; a list too long for the 32-bit scan
-        for i in (0, 3, 5, 6, 7, 8, 9):
-            assert _raw(p, buf.size, 40, flags, st, skip=i)[0] == _lib.CRC32C_EINVAL, i
-        assert _raw(p, buf.size, (2**32 - 2) // 43 + 1, flags, st)[0] == _lib.CRC32C_EINVAL
-        assert unchanged()
+        refused = [raw.repair_headers(dev, buf, many, null=(name,))
+                   for name in ("buf", "offsets", "ok", "bit", "lens", "nrepaired", "nbad")]
+        refused.append(raw.repair_headers(dev, buf, many, n=(2**32 - 2) // 43 + 1))
+        for got in refused:
+            assert got["rc"] == _lib.CRC32C_EINVAL
+            raw.expect_unchanged(got, buf)
         # offsets with no header to read, beside two that have one
-        q = [p[0], p[1] + 40 * 8] + p[2:]
-        assert _raw(q, buf.size, 5, flags | _lib.CRC32C_LOCATE_ONLY, st) == (_lib.CRC32C_OK, 1, 3) and unchanged()
-        assert got(2)[:5].tolist() == [0, 0, 0, REPAIRED, 1]
-        assert got(3).view(np.uint64)[:5].tolist() == [NO_BIT] * 3 + [256 + 3, NO_BIT]
-        assert got(4).view(np.uint32)[:5].tolist() == [0, 0, 0, nt, 110000]
-        assert _lib.lib.crc32c_last_kernel_ms() > 0
+        got = raw.repair_headers(dev, buf, few, locate_only=True)
+        ms = _lib.lib.crc32c_last_kernel_ms()
+        assert words(got) == (_lib.CRC32C_OK, 1, 3)
+        raw.expect_unchanged(got, buf)
+        assert got["ok"][:5].tolist() == [0, 0, 0, REPAIRED, 1]
+        assert got["bit"][:5].tolist() == [NO_BIT] * 3 + [256 + 3, NO_BIT]
+        assert got["lens"][:5].tolist() == [0, 0, 0, nt, 110000]
+        assert ms > 0
     with pytest.raises(mc.Crc32cError) as e:
         mc.repair_headers(buf.copy(), many)
     assert e.value.rc == _lib.CRC32C_EWORK

@@ -18,6 +18,7 @@ from memcached_amd import _lib
 from memcached_amd import crc32c as mc
 
 from . import oracle
+from . import raw_calls
 from .routes_cases import WBUF
 from .routes_cases import items_case as _items_case
 from .routes_cases import items_want as _items_want
@@ -30,10 +31,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def torch():
-    import torch as t
-    assert t.cuda.is_available(), "GPU tests need a visible MI355X"
-    assert mc.gpu_count() >= 1, "libmcrc32c.so sees no gfx950 device"
-    return t
+    return raw_calls.need_gpu()
 
 
 def _dev(torch, arr):

@@ -11,51 +11,28 @@ import pytest
 
 from memcached_amd import _lib
 from memcached_amd import crc32c as mc
+from tests import raw_calls as raw
 from tests import salvage_cases as sc
 from tests import salvage_model as sm
+from tests.salvage_cases import SMALL
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5A5A5A5A5A5A5A5A
+OK = _lib.CRC32C_OK
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _call(buf, W, walked, ok, cap, dev, cflags64=False, null_offsets=False):
-    """One library call.  Returns (rc, the whole offsets array of cap + 4
-    words pre-filled with SENT, nfound, scanned, ncand); checks that the
-    buffer and the lists are unchanged."""
-    nf, ns, nc = (ctypes.c_uint64(SENT) for _ in range(3))
-    fl = (_lib.CRC32C_CFLAGS64 if cflags64 else 0) | (_lib.CRC32C_DEVICE if dev else 0)
+def _expect(buf, W, walked, ok, cap, dev, want, tag="", **kw):
+    """One call on one route against want -- (rc, the offsets, nfound, scanned,
+    ncand) -- cut at cap, nothing behind it; the buffer and the caller's lists
+    are unchanged."""
     n = 0 if walked is None else len(walked)
-    if dev:
-        torch = _torch()
-        dbuf = torch.from_numpy(buf).cuda()
-        dw = torch.from_numpy(np.asarray(walked).astype(np.int64)).cuda() if n else None
-        dk = torch.from_numpy(np.asarray(ok, np.uint8)).cuda() if n else None
-        out = torch.full((cap + 4,), SENT, dtype=torch.int64, device="cuda")
-        rc = _lib.lib.crc32c_salvage_pages(dbuf.data_ptr(), buf.size, W, dw.data_ptr() if n else None,
-                                           dk.data_ptr() if n else None, n, None if null_offsets else out.data_ptr(),
-                                           cap, ctypes.byref(nf), ctypes.byref(ns), ctypes.byref(nc), fl,
-                                           torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        assert torch.equal(dbuf.cpu(), torch.from_numpy(buf)), "base was written"
-        if n:
-            assert np.array_equal(dw.cpu().numpy().astype(np.uint64), np.asarray(walked, np.uint64))
-            assert np.array_equal(dk.cpu().numpy(), np.asarray(ok, np.uint8))
-        got = out.cpu().numpy().astype(np.uint64)
-    else:
-        keep = buf.copy()
-        hw = np.ascontiguousarray(walked, np.uint64) if n else None
-        hk = np.ascontiguousarray(ok, np.uint8) if n else None
-        got = np.full(cap + 4, SENT, np.uint64)
-        rc = _lib.lib.crc32c_salvage_pages(buf.ctypes.data, buf.size, W, hw.ctypes.data if n else None,
-                                           hk.ctypes.data if n else None, n, None if null_offsets else got.ctypes.data,
-                                           cap, ctypes.byref(nf), ctypes.byref(ns), ctypes.byref(nc), fl, None)
-        assert np.array_equal(buf, keep), "base was written"
-    return rc, got, nf.value, ns.value, nc.value
+    walked = np.ascontiguousarray(walked, np.uint64) if n else None
+    ok = np.ascontiguousarray(ok, np.uint8) if n else None
+    got = raw.salvage_pages(dev, buf, W, walked, ok, cap=cap, **kw)
+    raw.expect_unchanged(got, buf)
+    if n:
+        assert np.array_equal(got["walked"], walked) and np.array_equal(got["walked_ok"], ok)
+    raw.expect_listed(got, cap, dict(zip(("rc", "offsets") + raw.SALVAGE_COUNTS, want)), raw.SALVAGE_COUNTS,
+                     arrays=("offsets",), tag=tag)
 
 
 def _lists(buf, W, cflags64=False):
@@ -76,18 +53,10 @@ def _check(buf, W, cfl=4, lists_opts=(False, True), small=(None, 0), routes=(Tru
         found, scanned, ncand, work = sm.salvage_fast(buf, W, walked, ok, cfl)
         assert work <= sm.WORK_MAX * (scanned + W)
         for sm_max in small:
-            prev = mc.set_small_max(sm_max) if sm_max is not None else None
-            try:
+            with raw.small_max(sm_max):
                 for dev in routes:
-                    rc, got, nf, ns, nc = _call(buf, W, walked, ok, len(found) + 3, dev, cf64)
-                    tag = (with_lists, sm_max, dev)
-                    assert rc == _lib.CRC32C_OK, tag
-                    assert (nf, ns, nc) == (len(found), scanned, ncand), tag
-                    assert got[:nf].tolist() == found, tag
-                    assert (got[nf:] == SENT).all(), tag
-            finally:
-                if prev is not None:
-                    mc.set_small_max(prev)
+                    _expect(buf, W, walked, ok, len(found) + 3, dev, (OK, found, len(found), scanned, ncand),
+                            (with_lists, sm_max, dev), cfl=cfl)
         results[with_lists] = (found, scanned, ncand)
     return results
 
@@ -95,12 +64,6 @@ def _check(buf, W, cfl=4, lists_opts=(False, True), small=(None, 0), routes=(Tru
 @pytest.fixture(scope="module")
 def cases():
     return sc.small_cases()
-
-
-SMALL = ["hdr_" + k for k in sc.HEADER_DAMAGE] + [
-    "data_only", "first_image", "last_image", "two_adjacent", "header_then_data", "ends_exact", "ends_one_short",
-    "lookalike_in_intact", "lookalike_in_damaged", "no_crlf", "cflags64", "cflags64_read_as_32", "config5_small",
-    "ranges_6", "ranges_over_64"]
 
 
 @pytest.mark.parametrize("name", SMALL)
@@ -135,9 +98,7 @@ def test_hand_made_lists(cases):
         walked, ok = np.array(lst, np.uint64), np.array(flags, np.uint8)
         found, scanned, ncand, _ = sm.salvage_bytewise(buf, W, walked, ok)
         for dev in (True, False):
-            rc, got, nf, ns, nc = _call(buf, W, walked, ok, 8, dev)
-            assert (rc, nf, ns, nc) == (_lib.CRC32C_OK, len(found), scanned, ncand), (lst, dev)
-            assert got[:nf].tolist() == found and (got[nf:] == SENT).all(), (lst, dev)
+            _expect(buf, W, walked, ok, 8, dev, (OK, found, len(found), scanned, ncand), (lst, dev))
     assert sm.salvage_bytewise(buf, W, np.array([0, 500, 1000, 2000]), np.array([1, 0, 0, 1]))[0] == [1000, 3000, 4000]
     # more than a round of entries, every third one dropped from the walk's list of a damaged wbuf
     buf, W, cfl = cases["ranges_over_64"]
@@ -147,9 +108,7 @@ def test_hand_made_lists(cases):
     found, scanned, ncand, _ = sm.salvage_fast(buf, W, walked, ok)
     assert len(found) > 64
     for dev in (True, False):
-        rc, got, nf, ns, nc = _call(buf, W, walked, ok, len(found) + 2, dev)
-        assert (rc, nf, ns, nc) == (_lib.CRC32C_OK, len(found), scanned, ncand), dev
-        assert got[:nf].tolist() == found and (got[nf:] == SENT).all(), dev
+        _expect(buf, W, walked, ok, len(found) + 2, dev, (OK, found, len(found), scanned, ncand), dev)
 
 
 def test_python_face_numpy_and_torch(cases):
@@ -158,7 +117,7 @@ def test_python_face_numpy_and_torch(cases):
     found, scanned, ncand, _ = sm.salvage_fast(buf, W, offs, ok)
     got, info = mc.salvage_pages(buf, W, offs, ok)
     assert got.tolist() == found and info == {"scanned": scanned, "ncand": ncand}
-    torch = _torch()
+    torch = raw.need_gpu()
     dbuf = torch.from_numpy(buf).cuda()
     doffs, dok, _ = mc.verify_pages(dbuf, W)
     got, info = mc.salvage_pages(dbuf, W, doffs, dok)
@@ -170,8 +129,7 @@ def test_python_face_numpy_and_torch(cases):
 def test_a_buffer_shorter_than_a_header():
     buf = sc.small_cases()["under_48_bytes"][0]
     for dev in (True, False):
-        rc, got, nf, ns, nc = _call(buf, sc.K16, None, None, 4, dev)
-        assert (rc, nf, ns, nc) == (_lib.CRC32C_OK, 0, 0, 0) and (got == SENT).all()
+        _expect(buf, sc.K16, None, None, 4, dev, (OK, [], 0, 0, 0), dev)
 
 
 @pytest.fixture(scope="module")
@@ -188,19 +146,13 @@ def test_every_alignment_and_tile_boundary(alignment):
     assert len(found) == 2 * 4200 and {o % 4096 for o in found} == set(range(4096))
     assert work <= sm.WORK_MAX * (scanned + W)
     for sm_max in (None, 0):
-        prev = mc.set_small_max(sm_max) if sm_max is not None else None
-        try:
+        with raw.small_max(sm_max):
             for dev in (True, False):
-                rc, got, nf, ns, nc = _call(buf, W, None, None, len(found) + 3, dev)
-                assert (rc, nf, ns, nc) == (_lib.CRC32C_OK, len(found), scanned, ncand), (sm_max, dev)
-                assert got[:nf].tolist() == found and (got[nf:] == SENT).all(), (sm_max, dev)
-        finally:
-            if prev is not None:
-                mc.set_small_max(prev)
+                _expect(buf, W, None, None, len(found) + 3, dev, (OK, found, len(found), scanned, ncand), (sm_max, dev))
     walked, ok = _lists(buf, W)
     assert walked.size == 0
     # a device buffer that starts off the tile grid and off a 16-byte boundary
-    torch = _torch()
+    torch = raw.need_gpu()
     pad = 4096 + 23
     dbig = torch.zeros(pad + 64 * W, dtype=torch.uint8, device="cuda")
     dbig[pad:] = torch.from_numpy(buf[:64 * W]).cuda()
@@ -232,12 +184,9 @@ def test_more_results_than_cap(cases):
     assert len(found) >= 3
     for dev in (True, False):
         for cap in (1, len(found) - 1, len(found)):
-            rc, got, nf, ns, nc = _call(buf, W, walked, ok, cap, dev)
-            assert (rc, nf, ns, nc) == (_lib.CRC32C_OK, len(found), scanned, ncand)
-            assert got[:cap].tolist() == found[:cap] and (got[cap:] == SENT).all()
+            _expect(buf, W, walked, ok, cap, dev, (OK, found, len(found), scanned, ncand), (dev, cap))
         # cap == 0 counts only; offsets may be NULL (the CRCs are still checked: nfound is exact)
-        rc, got, nf, ns, nc = _call(buf, W, walked, ok, 0, dev, null_offsets=True)
-        assert (rc, nf, ns, nc) == (_lib.CRC32C_OK, len(found), scanned, ncand) and (got == SENT).all()
+        _expect(buf, W, walked, ok, 0, dev, (OK, found, len(found), scanned, ncand), (dev, 0), null_arrays=True)
     # scanned and ncand may be NULL
     n = ctypes.c_uint64(0)
     rc = _lib.lib.crc32c_salvage_pages(buf.ctypes.data, buf.size, W, None, None, 0, None, 0, ctypes.byref(n), None,
@@ -251,9 +200,7 @@ def test_the_work_bound():
     found, scanned, ncand, work = sm.salvage_fast(buf, W, walked, ok)
     assert work > sm.WORK_MAX * (scanned + W)
     for dev in (True, False):
-        rc, got, nf, ns, nc = _call(buf, W, walked, ok, 16, dev)
-        assert (rc, nf, ns, nc) == (_lib.CRC32C_EWORK, 0, scanned, ncand)
-        assert (got == SENT).all()
+        _expect(buf, W, walked, ok, 16, dev, (_lib.CRC32C_EWORK, [], 0, scanned, ncand), dev)
     with pytest.raises(mc.Crc32cError) as e:
         mc.salvage_pages(buf, W, walked, ok)
     assert e.value.rc == _lib.CRC32C_EWORK and e.value.ncand == ncand and e.value.scanned == scanned
@@ -271,9 +218,7 @@ def test_bad_lists_are_refused(cases):
     for name, lst in bad.items():
         flags = np.ones(lst.size, np.uint8)
         for dev in (True, False):
-            rc, got, nf, ns, nc = _call(buf, W, lst, flags, 8, dev)
-            assert rc == _lib.CRC32C_EINVAL, (name, dev)
-            assert (nf, ns, nc) == (SENT, SENT, SENT) and (got == SENT).all(), (name, dev)
+            _expect(buf, W, lst, flags, 8, dev, (_lib.CRC32C_EINVAL, []) + (raw.SENT64,) * 3, (name, dev))
     # and the call still works afterwards
-    rc, got, nf, ns, nc = _call(buf, W, walked, ok, 64, True)
-    assert rc == _lib.CRC32C_OK and got[:nf].tolist() == sm.salvage_fast(buf, W, walked, ok)[0]
+    found, scanned, ncand, _ = sm.salvage_fast(buf, W, walked, ok)
+    _expect(buf, W, walked, ok, 64, True, (OK, found, len(found), scanned, ncand))

@@ -12,24 +12,16 @@ import pytest
 
 from memcached_amd import _lib
 from memcached_amd import crc32c as mc
+from tests import raw_calls as raw
 from tests import scrub_cases as sca
 from tests import scrub_model as scm
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5A5A5A5A5A5A5A5A
-SENT32, SENT8 = SENT & 0xFFFFFFFF, SENT & 0xFF
-EXTRA = 4  # sentinel words behind each array's room
-LISTS = ("offsets", "lens", "kind", "flip_offsets", "flip_bits", "flip_by")
-DTYPES = (np.uint64, np.uint32, np.uint8, np.uint64, np.uint64, np.uint8)
-WORDS = scm.COUNTS + ("nflips", "headers_repaired", "items_repaired", "rounds", "complete")
+LISTS, DTYPES = zip(*raw.SCRUB_LISTS)
+WORDS = raw.SCRUB_WORDS
 NAMES = list(sca.CASES)
 ROUTES = [pytest.param(True, id="device"), pytest.param(False, id="host")]
 _MODEL = {}
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def model(name, **more):
@@ -38,60 +30,6 @@ def model(name, **more):
         buf, W, cfl, kw, _ = sca.case(name)
         _MODEL[key] = scm.scrub(buf, W, cfl, **dict(kw, **more))
     return _MODEL[key]
-
-
-def call(buf, W, dev, cap, flip_cap, cfl=4, max_span=0, max_rounds=0, locate_only=False, null_arrays=False,
-         dbuf=None):
-    """One crc32c_scrub_pages over a copy of buf (host) or its device copy.
-    The six arrays have cap + EXTRA / flip_cap + EXTRA words, pre-filled with
-    the sentinel, and the struct's counts hold it too.  Returns the result in
-    the model's shape, the arrays whole under "raw", and "after"."""
-    mode = (_lib.CRC32C_DEVICE if dev else 0) | (_lib.CRC32C_CFLAGS64 if cfl == 8 else 0) | (
-        _lib.CRC32C_LOCATE_ONLY if locate_only else 0)
-    rooms = (cap, cap, cap, flip_cap, flip_cap, flip_cap)
-    if dev:
-        torch = _torch()
-        kinds = ((SENT, torch.int64), (SENT32, torch.int32), (SENT8, torch.uint8), (SENT, torch.int64), (SENT, torch.int64),
-                 (SENT8, torch.uint8))
-        arrays = [torch.full((n + EXTRA,), s, dtype=t, device="cuda") for n, (s, t) in zip(rooms, kinds)]
-        ptrs = [a.data_ptr() for a in arrays]
-        page = torch.from_numpy(buf.copy()).cuda() if dbuf is None else dbuf
-        base, stream = page.data_ptr(), torch.cuda.current_stream().cuda_stream
-    else:
-        kinds = ((SENT, np.uint64), (SENT32, np.uint32), (SENT8, np.uint8), (SENT, np.uint64), (SENT, np.uint64),
-                 (SENT8, np.uint8))
-        arrays = [np.full(n + EXTRA, s, t) for n, (s, t) in zip(rooms, kinds)]
-        ptrs = [a.ctypes.data for a in arrays]
-        page = buf.copy()
-        base, stream = page.ctypes.data, None
-    if null_arrays:
-        ptrs = [None if room == 0 else p for p, room in zip(ptrs, rooms)]
-    opts = _lib.ScrubOpts(mode, max_span, max_rounds, stream)
-    out = _lib.ScrubOut(*ptrs[:3], cap, *ptrs[3:], flip_cap, *([SENT] * 9), SENT32, SENT32)
-    rc = _lib.lib.crc32c_scrub_pages(base, buf.size, W, ctypes.byref(opts), ctypes.byref(out))
-    if dev:
-        torch.cuda.synchronize()
-        raw = [a.cpu().numpy().astype(d) for a, d in zip(arrays, DTYPES)]
-        after = page.cpu().numpy()
-    else:
-        raw, after = arrays, page
-    got = {w: int(getattr(out, w)) for w in WORDS}
-    got.update(rc=rc, raw=dict(zip(LISTS, raw)), after=after, rooms=dict(zip(LISTS, rooms)), ms=mc.lib.crc32c_last_kernel_ms())
-    return got
-
-
-def check(got, m, after=None):
-    """got against the model's result m, exactly; after: the bytes expected."""
-    assert got["rc"] == m["rc"]
-    assert {w: got[w] for w in WORDS} == {w: m[w] for w in WORDS}
-    for name in LISTS:
-        total = m["nitems"] if name in LISTS[:3] else m["nflips"]
-        room, raw = got["rooms"][name], got["raw"][name]
-        k = min(room, total)
-        assert raw[:k].tolist() == m[name][:k], name
-        sent = SENT if raw.dtype == np.uint64 else SENT32 if raw.dtype == np.uint32 else SENT8
-        assert (raw[k:] == sent).all(), f"{name}: written behind its first {k}"
-    assert (got["after"] == (m["after"] if after is None else after)).all()
 
 
 def written_out(page, W, cfl, max_span=0, max_rounds=0):
@@ -103,7 +41,8 @@ def written_out(page, W, cfl, max_span=0, max_rounds=0):
     nbytes = page.numel() if mc._is_torch(page) else page.size
     host = (lambda a: a.cpu().numpy()) if mc._is_torch(page) else (lambda a: a)
     lst = lambda a, d: host(a).astype(d).tolist()  # noqa: E731
-    dev_list = (lambda todo: _torch().tensor(todo, dtype=_torch().int64, device="cuda")) if mc._is_torch(page) else (
+    torch = raw.need_gpu() if mc._is_torch(page) else None
+    dev_list = (lambda todo: torch.tensor(todo, dtype=torch.int64, device="cuda")) if torch else (
         lambda todo: np.array(todo, np.uint64))
 
     def triage():
@@ -139,12 +78,12 @@ def written_out(page, W, cfl, max_span=0, max_rounds=0):
 def test_scrub_matches_the_model_and_the_written_out_flow(name, dev):
     buf, W, cfl, kw, notes = sca.case(name)
     m = model(name)
-    got = call(buf, W, dev, m["nitems"], m["nflips"], cfl, **kw)
-    check(got, m)
+    got = raw.scrub_pages(dev, buf, W, cap=m["nitems"], flip_cap=m["nflips"], cfl=cfl, **kw)
+    raw.expect_scrub(got, m)
     assert got["ms"] >= 0.0
     if m["rc"] != 0:
         return  # (the Python face raises past the work bound: the written-out flow ends there too)
-    page = _torch().from_numpy(buf.copy()).cuda() if dev else buf.copy()
+    page = raw.need_gpu().from_numpy(buf.copy()).cuda() if dev else buf.copy()
     T, log, rounds, complete = written_out(page, W, cfl, **kw)
     assert [list(x) for x in T] == [m["offsets"], m["lens"], m["kind"]]
     assert log == list(zip(m["flip_offsets"], m["flip_bits"], m["flip_by"]))
@@ -161,28 +100,30 @@ def test_small_outputs(name, dev):
     m = model(name)
     for cap in (0, m["nitems"] - 1, m["nitems"] + 2):
         for flip_cap in (0, m["nflips"] - 1, m["nflips"] + 2):
-            check(call(buf, W, dev, cap, flip_cap, cfl, null_arrays=True, **kw), m)
+            got = raw.scrub_pages(dev, buf, W, cap=cap, flip_cap=flip_cap, cfl=cfl, null_arrays=True, **kw)
+            raw.expect_scrub(got, m)
 
 
 @pytest.mark.parametrize("name", ["second_pass", "suspect_promotion_cflags64"])
 def test_host_locate_only(name):
     buf, W, cfl, kw, _ = sca.case(name)
     m = model(name)
-    got = call(buf, W, False, m["nitems"], m["nflips"], cfl, locate_only=True, **kw)
-    check(got, m, after=buf)
-    replayed = scm.replay(buf, {k: got["raw"][k][:m["nflips"]].tolist() for k in ("flip_offsets", "flip_bits")})
-    assert (replayed == call(buf, W, False, m["nitems"], m["nflips"], cfl, **kw)["after"]).all()
+    caps = dict(cap=m["nitems"], flip_cap=m["nflips"], cfl=cfl)
+    got = raw.scrub_pages(False, buf, W, locate_only=True, **caps, **kw)
+    raw.expect_scrub(got, m, after=buf)
+    replayed = scm.replay(buf, {k: got[k][:m["nflips"]].tolist() for k in ("flip_offsets", "flip_bits")})
+    assert (replayed == raw.scrub_pages(False, buf, W, **caps, **kw)["after"]).all()
 
 
 def _untouched(got, buf):
-    assert all(got[w] == (SENT32 if w in ("rounds", "complete") else SENT) for w in WORDS)
-    assert all((got["raw"][k] == got["raw"][k][-1]).all() for k in LISTS)
+    assert all(got[w] == (raw.SENT[4] if w in ("rounds", "complete") else raw.SENT64) for w in WORDS)
+    assert all((got[k] == got[k][-1]).all() for k in LISTS)
     assert (got["after"] == buf).all()
 
 
 def test_device_locate_only_is_refused():
     buf, W, cfl, kw, _ = sca.case("second_pass")
-    got = call(buf, W, True, 8, 8, cfl, locate_only=True)
+    got = raw.scrub_pages(True, buf, W, cap=8, flip_cap=8, cfl=cfl, locate_only=True)
     assert got["rc"] == _lib.CRC32C_EINVAL
     _untouched(got, buf)
 
@@ -190,10 +131,10 @@ def test_device_locate_only_is_refused():
 @pytest.mark.parametrize("dev", ROUTES)
 def test_invalid_arguments_write_nothing(dev):
     buf, W, cfl, kw, _ = sca.case("second_pass")
-    got = call(buf, 0, dev, 8, 8)
+    got = raw.scrub_pages(dev, buf, 0, cap=8, flip_cap=8)
     assert got["rc"] == _lib.CRC32C_EINVAL
     _untouched(got, buf)
-    got = call(buf, W, dev, 8, 8, max_span=_lib.CRC32C_REPAIR_SPAN_MAX + 1)
+    got = raw.scrub_pages(dev, buf, W, cap=8, flip_cap=8, max_span=_lib.CRC32C_REPAIR_SPAN_MAX + 1)
     assert got["rc"] == _lib.CRC32C_EINVAL
     _untouched(got, buf)
     out = _lib.ScrubOut(None, None, None, 1, None, None, None, 0)
@@ -211,7 +152,10 @@ def test_invalid_arguments_write_nothing(dev):
 @pytest.mark.parametrize("dev", ROUTES)
 def test_empty_page_and_null_opts(dev):
     buf, W, cfl, kw, _ = sca.case("kind0_entry")
-    got = call(buf[:0], W, dev, 0, 0, dbuf=_torch().zeros(16, dtype=_torch().uint8, device="cuda") if dev else None)
+    side = raw.Side(where=dev)
+    if dev:
+        side.adopt(side.torch.zeros(16, dtype=side.torch.uint8, device="cuda"))
+    got = raw.scrub_pages(side, buf[:0], W, cap=0, flip_cap=0)
     if not dev:  # (a host array of no bytes has an address all the same)
         assert got["rc"] == 0 and got["complete"] == 1
         assert all(got[w] == 0 for w in WORDS if w != "complete")
@@ -230,10 +174,10 @@ def test_empty_page_and_null_opts(dev):
 def test_second_call_changes_nothing(dev):
     buf, W, cfl, kw, _ = sca.case("dropped_lookalike")
     m = model("dropped_lookalike")
-    again = call(m["after"], W, dev, m["nitems"], 4, cfl)
+    again = raw.scrub_pages(dev, m["after"], W, cap=m["nitems"], flip_cap=4, cfl=cfl)
     assert again["nflips"] == 0 and again["rounds"] == 0 and again["complete"] == 1 and again["rc"] == 0
-    assert again["raw"]["offsets"][:m["nitems"]].tolist() == m["offsets"]
-    assert again["raw"]["kind"][:m["nitems"]].tolist() == m["kind"]
+    assert again["offsets"][:m["nitems"]].tolist() == m["offsets"]
+    assert again["kind"][:m["nitems"]].tolist() == m["kind"]
     assert (again["after"] == m["after"]).all()
 
 
@@ -241,7 +185,7 @@ def test_second_call_changes_nothing(dev):
 def test_python_face(dev):
     buf, W, cfl, kw, _ = sca.case("second_pass")
     m = model("second_pass")
-    page = _torch().from_numpy(buf.copy()).cuda() if dev else buf.copy()
+    page = raw.need_gpu().from_numpy(buf.copy()).cuda() if dev else buf.copy()
     *arrays, info = mc.scrub_pages(page, W)
     host = [(a.cpu().numpy() if dev else a) for a in arrays]
     for a, name, d in zip(host, LISTS, DTYPES):

@@ -12,88 +12,44 @@ import pytest
 
 from memcached_amd import _lib
 from memcached_amd import crc32c as mc
+from tests import raw_calls as raw
 from tests import triage_cases as tc
 from tests import triage_model as tm
-from tests.test_gpu_salvage import SMALL
+from tests.salvage_cases import SMALL
 
 pytestmark = pytest.mark.gpu
-SENT = 0x5A5A5A5A5A5A5A5A
-SENT32, SENT8 = SENT & 0xFFFFFFFF, SENT & 0xFF
-COUNTS = ("nitems", "nbad", "nsalvaged", "nsuspect", "scanned", "ncand")
-RCOUNTS = tuple(c for c in COUNTS if c != "nsuspect")
+COUNTS, RCOUNTS = raw.TRIAGE_COUNTS, raw.RECOVER_COUNTS
 SUSPECT = _lib.CRC32C_ITEM_SUSPECT
 BUILT = ["behind_nkey0", "walked_bad_is_not_listed_twice", "suspect_inside_found", "found_inside_suspect",
          "many_rounds", "work_bound"]
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _flags(dev, cflags64):
-    return (_lib.CRC32C_CFLAGS64 if cflags64 else 0) | (_lib.CRC32C_DEVICE if dev else 0)
-
-
-def _call(buf, W, cap, dev, cflags64=False, null_arrays=False, dbuf=None, triage=True):
-    """One call of crc32c_triage_pages (or crc32c_recover_pages) over buf (host)
-    or its device copy (dbuf: one the caller placed).  Returns (rc, offsets, lens,
-    kind -- cap + 4 words each, pre-filled with the sentinel -- and the counts);
-    checks that the buffer is unchanged."""
-    fn = _lib.lib.crc32c_triage_pages if triage else _lib.lib.crc32c_recover_pages
-    names = COUNTS if triage else RCOUNTS
-    counts = [ctypes.c_uint64(SENT) for _ in names]
-    refs = [ctypes.byref(c) for c in counts]
-    if dev:
-        torch = _torch()
-        if dbuf is None:
-            dbuf = torch.from_numpy(buf).cuda()
-        out = [torch.full((cap + 4,), s, dtype=t, device="cuda")
-               for s, t in ((SENT, torch.int64), (SENT32, torch.int32), (SENT8, torch.uint8))]
-        ptrs = [None] * 3 if null_arrays else [o.data_ptr() for o in out]
-        rc = fn(dbuf.data_ptr(), buf.size, W, *ptrs, cap, *refs, _flags(True, cflags64),
-                torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        assert torch.equal(dbuf.cpu(), torch.from_numpy(buf)), "base was written"
-        got = [o.cpu().numpy().astype(d) for o, d in zip(out, (np.uint64, np.uint32, np.uint8))]
-    else:
-        keep = buf.copy()
-        got = [np.full(cap + 4, s, d) for s, d in ((SENT, np.uint64), (SENT32, np.uint32), (SENT8, np.uint8))]
-        ptrs = [None] * 3 if null_arrays else [g.ctypes.data for g in got]
-        rc = fn(buf.ctypes.data, buf.size, W, *ptrs, cap, *refs, _flags(False, cflags64), None)
-        assert np.array_equal(buf, keep), "base was written"
-    return (rc, *got, dict(zip(names, (c.value for c in counts))))
-
-
-def _expect(got, cap, m, tag, names=COUNTS):
-    """One call's results against a model dict, cut at cap; nothing behind it."""
-    grc, goffs, glens, gkind, gcounts = got
-    assert grc == m["rc"], tag
-    assert gcounts == {k: m[k] for k in names}, tag
-    k = min(cap, len(m["offsets"]))
-    assert goffs[:k].tolist() == m["offsets"][:k] and gkind[:k].tolist() == m["kind"][:k], tag
-    assert glens[:k].tolist() == m["lens"][:k], tag
-    assert (goffs[k:] == SENT).all() and (glens[k:] == SENT32).all() and (gkind[k:] == SENT8).all(), tag
+def _call(buf, W, cap, dev, cfl=4, null_arrays=False, side=None, triage=True):
+    """One call of crc32c_triage_pages (or crc32c_recover_pages) over a copy of
+    buf on one route (side: one that holds a buffer the caller placed); the
+    buffer is unchanged."""
+    got = raw.listed_pages("crc32c_triage_pages" if triage else "crc32c_recover_pages", dev if side is None else side,
+                           buf, W, cap=cap, cfl=cfl, null_arrays=null_arrays)
+    raw.expect_unchanged(got, buf)
+    return got
 
 
 def _as_model(got):
-    rc, offs, lens, kind, counts = got
-    n = counts["nitems"]
-    return dict(counts, rc=rc, offsets=offs[:n].tolist(), lens=lens[:n].tolist(), kind=kind[:n].tolist())
+    n = got["nitems"]
+    return dict(got, offsets=got["offsets"][:n].tolist(), lens=got["lens"][:n].tolist(), kind=got["kind"][:n].tolist())
 
 
 def _check(buf, W, cfl, m, routes=(True, False)):
     """Every route of one buffer against the model, and against
     crc32c_recover_pages on the same buffer with kind 6 taken out."""
-    cf64 = cfl == 8
     cap = m["nitems"] + 3
     for dev in routes:
-        got = _call(buf, W, cap, dev, cf64)
-        _expect(got, cap, m, dev)
-        rec = _call(buf, W, cap, dev, cf64, triage=False)
+        got = _call(buf, W, cap, dev, cfl)
+        raw.expect_listed(got, cap, m, COUNTS, tag=dev)
+        rec = _call(buf, W, cap, dev, cfl, triage=False)
         mine = tm.without_suspects(_as_model(got))
-        _expect(rec, cap, mine, ("recover", dev), RCOUNTS)
-        assert rec[4]["nitems"] == got[4]["nitems"] - got[4]["nsuspect"]
+        raw.expect_listed(rec, cap, mine, RCOUNTS, tag=("recover", dev))
+        assert rec["nitems"] == got["nitems"] - got["nsuspect"]
 
 
 @pytest.fixture(scope="module")
@@ -136,9 +92,9 @@ def test_caps(cases, models):
     assert m["kind"][cut] == _lib.CRC32C_ITEM_SALVAGED and 1 < cut < n
     for dev in (True, False):
         for cap in (1, cut, n):
-            _expect(_call(buf, W, cap, dev), cap, m, (dev, cap))
+            raw.expect_listed(_call(buf, W, cap, dev), cap, m, COUNTS, tag=(dev, cap))
         # cap == 0: everything is still computed, the arrays may be NULL
-        _expect(_call(buf, W, 0, dev, null_arrays=True), 0, m, (dev, 0))
+        raw.expect_listed(_call(buf, W, 0, dev, null_arrays=True), 0, m, COUNTS, tag=(dev, 0))
     # scanned and ncand may be NULL; nsuspect may not
     c = [ctypes.c_uint64(0) for _ in range(4)]
     rc = _lib.lib.crc32c_triage_pages(buf.ctypes.data, buf.size, W, None, None, None, 0, *map(ctypes.byref, c), None,
@@ -161,28 +117,25 @@ def test_a_device_buffer_off_the_tile_grid(cases, models):
     """base + 1 .. base + 15: off the scan's 4 KiB tiles and off every 16-byte boundary."""
     buf, W, cfl, _ = cases["behind_nkey0"]
     m = models["behind_nkey0"]
-    torch = _torch()
+    torch = raw.need_gpu()
     dbig = torch.zeros(16 + buf.size, dtype=torch.uint8, device="cuda")
     cap = m["nitems"] + 3
     src = torch.from_numpy(buf).cuda()
     for pad in range(1, 16):
         dbig[pad:pad + buf.size] = src
-        _expect(_call(buf, W, cap, True, dbuf=dbig[pad:pad + buf.size]), cap, m, pad)
+        got = _call(buf, W, cap, True, side=raw.Side(torch).adopt(dbig[pad:pad + buf.size]))
+        raw.expect_listed(got, cap, m, COUNTS, tag=pad)
 
 
 def test_a_page_locked_and_a_pageable_host_buffer(cases, models):
     buf, W, cfl, _ = cases["many_rounds"]
     m = models["many_rounds"]
     cap = m["nitems"] + 3
-    _expect(_call(buf.copy(), W, cap, False), cap, m, "pageable")
-    p = _lib.lib.crc32c_host_alloc(buf.size)
-    assert p
-    try:
-        pinned = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), (buf.size,))
+    raw.expect_listed(_call(buf.copy(), W, cap, False), cap, m, COUNTS, tag="pageable")
+    with raw.pinned(buf.size) as pinned:
         pinned[:] = buf
-        _expect(_call(pinned, W, cap, False), cap, m, "pinned")
-    finally:
-        _lib.lib.crc32c_host_free(p)
+        got = _call(buf, W, cap, False, side=raw.Side(where="host").adopt(pinned))
+        raw.expect_listed(got, cap, m, COUNTS, tag="pinned")
 
 
 def test_python_face_numpy_and_torch(cases, models):
@@ -192,7 +145,7 @@ def test_python_face_numpy_and_torch(cases, models):
     offs, lens, kind, got = mc.triage_pages(buf, W)
     assert (offs.dtype, lens.dtype, kind.dtype) == (np.uint64, np.uint32, np.uint8)
     assert (offs.tolist(), lens.tolist(), kind.tolist(), got) == (m["offsets"], m["lens"], m["kind"], info)
-    torch = _torch()
+    torch = raw.need_gpu()
     offs, lens, kind, got = mc.triage_pages(torch.from_numpy(buf).cuda(), W)
     assert offs.is_cuda and lens.is_cuda and kind.is_cuda
     assert (offs.cpu().tolist(), lens.cpu().tolist(), kind.cpu().tolist(), got) == (m["offsets"], m["lens"], m["kind"],
@@ -256,11 +209,11 @@ def test_recover_before_and_after_a_triage_call(cases, models):
     cap = models["many_rounds"]["nitems"] + 3
     for dev in (True, False):
         before = _call(buf, W, cap, dev, triage=False)
-        _expect(_call(other, W2, models["behind_nkey0"]["nitems"] + 3, dev), models["behind_nkey0"]["nitems"] + 3,
-                models["behind_nkey0"], dev)
-        _expect(_call(buf, W, cap, dev), cap, models["many_rounds"], dev)
+        cap2 = models["behind_nkey0"]["nitems"] + 3
+        raw.expect_listed(_call(other, W2, cap2, dev), cap2, models["behind_nkey0"], COUNTS, tag=dev)
+        raw.expect_listed(_call(buf, W, cap, dev), cap, models["many_rounds"], COUNTS, tag=dev)
         after = _call(buf, W, cap, dev, triage=False)
-        assert before[0] == after[0] == _lib.CRC32C_OK and before[4] == after[4]
-        for a, b in zip(before[1:4], after[1:4]):
-            assert np.array_equal(a, b)
-        _expect(after, cap, tm.without_suspects(models["many_rounds"]), ("recover", dev), RCOUNTS)
+        assert before["rc"] == after["rc"] == _lib.CRC32C_OK and all(before[k] == after[k] for k in RCOUNTS)
+        for name, _ in raw.LISTED:
+            assert np.array_equal(before[name], after[name])
+        raw.expect_listed(after, cap, tm.without_suspects(models["many_rounds"]), RCOUNTS, tag=("recover", dev))

@@ -5,39 +5,23 @@ No GPU and no library call to build them; tests/test_gpu_interleave_triage.py
 runs them among that table's ops, and tests/test_triage_interleave_cases.py
 checks that the three tables together reach every batch entry point of
 include/crc32c_batch.h."""
-import ctypes
 import functools
 
 import numpy as np
 
 from . import interleave_cases as ic
+from . import raw_calls
+from .raw_calls import _capped
 from . import triage_cases as tc
 from . import triage_model as tm
 
 ENTRY = "crc32c_triage_pages"
-COUNTS = ("nitems", "nbad", "nsalvaged", "nsuspect", "scanned", "ncand")
+COUNTS = raw_calls.TRIAGE_COUNTS
 
 
 def _call_triage(op, side):
-    from memcached_amd import _lib
     i = op.inputs
-    buf = side.data(i["buf"])
-    cap = i["cap"]
-    offs, lens, kind = side.out(cap, np.uint64), side.out(cap, np.uint32), side.out(cap, np.uint8)
-    counts = [ctypes.c_uint64(ic.SENT64) for _ in COUNTS]
-    rc = _lib.lib.crc32c_triage_pages(ic.ptr(buf), i["buf"].size, i["wbuf"], ic.ptr(offs), ic.ptr(lens), ic.ptr(kind),
-                                      cap, *map(ctypes.byref, counts), side.flags, side.handle)
-    got = {"rc": rc, "offsets": side.host(offs, np.uint64), "lens": side.host(lens, np.uint32),
-           "kind": side.host(kind, np.uint8), "buf": side.host(buf, np.uint8)}
-    got.update(zip(COUNTS, (c.value for c in counts)))
-    return got
-
-
-def _capped(values, cap, dtype):
-    a = np.full(cap, ic.SENT[np.dtype(dtype).itemsize], dtype)
-    k = min(cap, len(values))
-    a[:k] = values[:k]
-    return ic.ended(a)
+    return ic._stated(op, raw_calls.listed_pages(ENTRY, side, i["buf"], i["wbuf"], cap=i["cap"]))
 
 
 def _op(name, where, buf, W, cfl, short=0):
