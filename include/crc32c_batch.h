@@ -560,7 +560,8 @@ uint64_t crc32c_locate_bit(uint32_t crc_computed, uint32_t crc_stored, uint64_t 
  * a separate, explicit call, not a mode of anything.  Run it after
  * crc32c_repair_items on what is still 0, or instead of it where those odds
  * are acceptable.  Damage spread over two bytes is
- * not located; crc32c_scrub_pages does not use this call.
+ * not located; crc32c_scrub_pages uses this call only where the caller sets
+ * CRC32C_SCRUB_BYTES, and logs its repairs apart (CRC32C_SCRUB_BY_BYTE).
  *
  * Everything else is crc32c_repair_items': the work bound (the spans of the
  * images with S != 0 and L <= max_span add up to more than base_bytes:
@@ -755,7 +756,58 @@ int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes
  * remain (as the walk reads a header: the 16-byte granules of its bytes
  * 28..43).  The other entry points ignore the bit.
  *
- * Outputs.  offsets / lens / kind take the first min(cap, nitems) entries of
+ * CRC32C_SCRUB_BYTES in opts->mode (opt-in; with the bit clear the call is
+ * exactly the above; it composes with CRC32C_SCRUB_GAPS) adds a third stage
+ * to the loop and nothing else: crc32c_repair_bytes, for the images whose
+ * damage is several bits of one byte, which the item stage drops.  The step
+ * "i repaired nothing: complete = 1, stop" becomes
+ *
+ *         i repaired nothing:
+ *           b = repair_bytes(L, bspan), in place, over the SAME list L the
+ *             item stage just ran on (item_list(T), or item_list'(T) with
+ *             CRC32C_SCRUB_GAPS); b failed: return its status;
+ *           b repaired nothing: complete = 1, stop (T describes the page);
+ *           log its flips, one more round, T = triage, stop at max_rounds,
+ *           else start the loop again (headers, then items, then bytes,
+ *           every time).
+ *
+ * bspan = CRC32C_REPAIR_BYTES_SPAN_DEFAULT when opts->max_span == 0, else
+ * min(opts->max_span, CRC32C_REPAIR_BYTES_SPAN_DEFAULT): the stage never
+ * searches longer spans than crc32c_repair_bytes does by default, and a caller
+ * who wants longer ones at worse odds makes that call themselves.  bspan is at
+ * most the item stage's resolved limit, so the byte stage's work sum is at
+ * most the item stage's over the same list and bytes: it cannot return
+ * CRC32C_EWORK where the item stage did not (a status that comes all the same
+ * is returned as any stage's is).
+ *
+ * The log stays one entry per inverted bit.  An image repaired at byte p with
+ * mask m contributes popcount(m) consecutive entries, in ascending bit order:
+ * flip_offsets = the image's offset, flip_bits = 8 p + b for every set bit b
+ * of m, flip_by = CRC32C_SCRUB_BY_BYTE; the images of a stage in list order.
+ * So the log's meaning holds (buffer bit 8 * offset + index; replaying the log
+ * on the damaged page gives the result), and flip_cap may cut between two bits
+ * of one byte: the first min(flip_cap, nflips) entries are written, nothing
+ * behind them, and nflips is exact.  nflips counts bits.  rounds counts the
+ * repair calls that repaired something, the byte stage's among them.
+ * items_repaired counts the images repaired by the item stage and the byte
+ * stage together (the struct has no room for a count of its own); the byte
+ * stage's share is the number of distinct flip_offsets among the
+ * CRC32C_SCRUB_BY_BYTE entries of the log.  With the bit set nflips ==
+ * headers_repaired + items_repaired no longer holds.  A single inverted bit is
+ * the item stage's, as before, and logged CRC32C_SCRUB_BY_ITEM: the byte stage
+ * runs only when the item stage repaired nothing.
+ *
+ * complete and the fixpoint property (a second call with the same mode on the
+ * result inverts nothing and returns the same list), max_rounds,
+ * CRC32C_LOCATE_ONLY (host only), the host staging, the error codes, the read
+ * and write bounds and crc32c_last_kernel_ms are unchanged.  The evidence is
+ * that of the calls composed: an image logged CRC32C_SCRUB_BY_BYTE carries
+ * crc32c_repair_bytes' odds, 255 (4 + L) / 2^32 with no even-weight guarantee,
+ * and suspects and gap starts, which nothing else proves, are handed to it
+ * too: the weakest evidence the scrub can give.  The log tells such images
+ * apart.  The other entry points ignore the bit.
+ *
+ * Outputs. offsets / lens / kind take the first min(cap, nitems) entries of
  * the last T, and nitems, nbad, nsalvaged, nsuspect, scanned and ncand are
  * its counts, all as crc32c_triage_pages reports them.  The log has one entry
  * per bit inverted, in the order made (round by round, in a round in list
@@ -802,14 +854,19 @@ int crc32c_repair_headers(void *base, uint64_t base_bytes, uint64_t region_bytes
  * and the repair calls' 9 B (items) or 13 B (headers) of verdicts; a host
  * call: the staged page and 17 B per flip of a round.  With
  * CRC32C_SCRUB_GAPS: 12 B per gap start, and where a triage has any, 14 B per
- * entry of the merged list and its gap starts together. */
+ * entry of the merged list and its gap starts together.  With
+ * CRC32C_SCRUB_BYTES: 1 B of mask per item-list entry, a host call 8 flip
+ * slots per image a byte stage repaired instead of 1, and one 8-byte count
+ * read back per byte stage that repaired something. */
 #define CRC32C_SCRUB_ROUNDS_DEFAULT 64
 #define CRC32C_SCRUB_BY_HEADER 1 /* flip_by[]: made by the crc32c_repair_headers stage */
 #define CRC32C_SCRUB_BY_ITEM 2   /* flip_by[]: made by the crc32c_repair_items stage */
+#define CRC32C_SCRUB_BY_BYTE 3   /* flip_by[]: made by the crc32c_repair_bytes stage */
 #define CRC32C_SCRUB_GAPS 0x40u  /* crc32c_scrub_opts.mode: list the gap starts too (above); other calls ignore it */
+#define CRC32C_SCRUB_BYTES 0x80u /* crc32c_scrub_opts.mode: the crc32c_repair_bytes stage (above); other calls ignore it */
 
 typedef struct crc32c_scrub_opts { /* NULL: all zero */
-    uint32_t mode;       /* CRC32C_DEVICE | CRC32C_CFLAGS64 | CRC32C_LOCATE_ONLY | CRC32C_SCRUB_GAPS; others ignored */
+    uint32_t mode;       /* CRC32C_DEVICE | CRC32C_CFLAGS64 | CRC32C_LOCATE_ONLY | CRC32C_SCRUB_GAPS | CRC32C_SCRUB_BYTES; others ignored */
     uint32_t max_span;   /* crc32c_repair_items' max_span, same meaning, same CRC32C_EINVAL */
     uint32_t max_rounds; /* 0: CRC32C_SCRUB_ROUNDS_DEFAULT */
     void *stream;

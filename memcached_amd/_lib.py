@@ -45,7 +45,9 @@ CRC32C_HEADER_WORK_MAX = 8  # its work bound: the candidate variants' spans per 
 CRC32C_SCRUB_ROUNDS_DEFAULT = 64  # crc32c_scrub_pages' max_rounds when 0 is passed
 CRC32C_SCRUB_BY_HEADER = 1  # its flip_by[]: made by the crc32c_repair_headers stage
 CRC32C_SCRUB_BY_ITEM = 2  # ... by the crc32c_repair_items stage
+CRC32C_SCRUB_BY_BYTE = 3  # ... by the crc32c_repair_bytes stage (CRC32C_SCRUB_BYTES)
 CRC32C_SCRUB_GAPS = 0x40  # crc32c_scrub_opts.mode: list the ends of the proven unreached images too
+CRC32C_SCRUB_BYTES = 0x80  # crc32c_scrub_opts.mode: crc32c_repair_bytes over the item list when the item stage repaired nothing
 CRC32C_MAX_SPAN = 0x7FFF0000  # longest span (include/crc32c_batch.h)
 CRC32C_SALVAGE_WORK_MAX = 64  # crc32c_salvage_pages' work bound: candidates' spans per scanned byte
 

@@ -36,8 +36,8 @@ import operator
 import numpy as np
 
 from . import _lib
-from ._lib import (CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, CRC32C_SCRUB_GAPS, Crc32cError, check,
-                   lib)
+from ._lib import (CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, CRC32C_SCRUB_BY_BYTE,
+                   CRC32C_SCRUB_BYTES, CRC32C_SCRUB_GAPS, Crc32cError, check, lib)
 
 # (recover_pages, triage_pages, repair_items, locate_bit, repair_headers, scrub_pages, repair_bytes and locate_byte are
 # public as well; tests/test_python_face.py pins this list as it stood before them)
@@ -610,7 +610,7 @@ def repair_headers(buf, item_offsets, region_bytes=0, locate_only=False, stream=
 
 
 def scrub_pages(buf, wbuf_bytes, max_span=0, max_rounds=0, locate_only=False, stream=None, cflags64=False,
-                gaps=False):
+                gaps=False, byte_rule=False):
     """A page's whole repair flow in one call (crc32c_scrub_pages):
     triage_pages, rounds of repair_headers over every kind-0 entry and each
     piece's walk end, repair_items over the damaged entries and the suspects
@@ -641,13 +641,22 @@ def scrub_pages(buf, wbuf_bytes, max_span=0, max_rounds=0, locate_only=False, st
     ``gaps`` sets CRC32C_SCRUB_GAPS: the end of every image found (kind 4)
     that is no entry's offset is handed to both repair stages as well, so an
     image with one flipped length or CRLF bit directly behind a proven one
-    comes back, one such image per round."""
+    comes back, one such image per round.
+
+    ``byte_rule`` sets CRC32C_SCRUB_BYTES: when the item stage repairs nothing,
+    repair_bytes runs over the same list (spans up to 64 KiB, or ``max_span``
+    when that is smaller), so an image with several bits of one byte inverted
+    comes back too.  Its flips are logged one entry per bit with
+    CRC32C_SCRUB_BY_BYTE, info["nflips"] counts bits and
+    info["items_repaired"] counts its images with the item stage's; such an
+    image carries repair_bytes' weaker evidence."""
     wbuf_bytes = _wbuf_bytes(wbuf_bytes)
     side = _side(buf, stream)
     buf, nbytes = side.buffer(buf, inplace=None if locate_only else
                               "scrub_pages needs {} (repaired in place) unless locate_only is set")
     mode = side.flag | _flags(cflags64) | (0 if side.dev and not locate_only else _lib.CRC32C_LOCATE_ONLY)
     mode |= CRC32C_SCRUB_GAPS if gaps else 0
+    mode |= CRC32C_SCRUB_BYTES if byte_rule else 0
     opts = _lib.ScrubOpts(mode, max_span, max_rounds, side.stream)
     cap = _walk_bound(nbytes, wbuf_bytes)
     if side.dev:

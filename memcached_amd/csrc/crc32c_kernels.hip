@@ -43,5 +43,5 @@
 #include "k_recover.h" // crc32c_recover_pages, crc32c_triage_pages: k_recover_regions, k_recover_merge
 #include "k_repair.h"  // crc32c_repair_items: k_repair_count, k_repair_emit, k_repair_search, k_repair_apply
 #include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply
-#include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_gaps, k_scrub_gap_merge, k_scrub_log
+#include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_gaps, k_scrub_gap_merge, k_scrub_log, k_scrub_log_bytes
 #include "k_repair_bytes.h"  // crc32c_repair_bytes: k_repair_bytes_search, k_repair_bytes_apply

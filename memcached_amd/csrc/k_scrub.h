@@ -16,7 +16,9 @@
 //                    ends at or before the next proven entry (kind 1 or 4) and
 //                    starts at or behind the end of the last suspect kept;
 //   k_scrub_log      a repair stage's verdicts compacted into the log, in list
-//                    order.
+//                    order;
+//   k_scrub_log_bytes  the same for a byte stage (CRC32C_SCRUB_BYTES): a
+//                    repaired entry's mask becomes one log entry per set bit.
 // The two list kernels run twice around a k_scan32, as the walk does: one wave
 // per piece, its entries 64 a round.  Both rules are piece-local: a piece's
 // entries are one range of the list, a suspect is a sane candidate and so lies
@@ -292,6 +294,57 @@ __global__ __launch_bounds__(kScrubLogThreads) void k_scrub_log(const uint64_t *
         }
         carry += all;
     }
+}
+
+// The log of a byte stage (CRC32C_SCRUB_BYTES): entry i of its list with
+// ok[i] = kItemRepaired, located at image byte byte[i] with mask[i], becomes
+// popcount(mask[i]) consecutive log entries (list[i], 8 byte[i] + b, by), one
+// per set bit b, ascending.  An entry's first log index is at plus the
+// popcounts of the repaired entries in front of it: a wave scan, the waves'
+// sums through LDS, and the carry of the rounds before.  Written only below
+// cap; *total takes the stage's exact bit count whatever cap is.  One
+// workgroup, kScrubLogThreads entries a round, as k_scrub_log.
+__global__ __launch_bounds__(kScrubLogThreads) void k_scrub_log_bytes(const uint64_t *list, const uint8_t *ok,
+                                                                      const uint64_t *byte, const uint8_t *mask,
+                                                                      uint64_t n, uint32_t by, uint64_t at,
+                                                                      uint64_t cap, uint64_t *flip_offsets,
+                                                                      uint64_t *flip_bits, uint8_t *flip_by,
+                                                                      unsigned long long *total) {
+    MCRC_VGPR_FLOOR();
+    __shared__ uint32_t sh[kScrubLogThreads / 64];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t carry = at;
+    for (uint64_t i0 = 0; i0 < n; i0 += kScrubLogThreads) {
+        const uint64_t i = i0 + threadIdx.x;
+        const bool hit = i < n && ok[i] == kItemRepaired;
+        const uint32_t m = hit ? mask[i] : 0u;
+        const uint32_t c = (uint32_t)__popc(m);
+        const uint32_t incl = wave_incl_scan(c, lane);
+        if (lane == 63) sh[w] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t k = 0; k < kScrubLogThreads / 64; ++k) {
+            before += k < w ? sh[k] : 0u;
+            all += sh[k];
+        }
+        __syncthreads();
+        if (m) {
+            uint64_t idx = carry + before + (incl - c);
+            const uint64_t o = list[i], k0 = 8 * byte[i];
+#pragma unroll
+            for (uint32_t b = 0; b < 8; ++b) {
+                if (!(m & (1u << b))) continue;
+                if (idx < cap) {
+                    flip_offsets[idx] = o;
+                    flip_bits[idx] = k0 + b;
+                    flip_by[idx] = (uint8_t)by;
+                }
+                ++idx;
+            }
+        }
+        carry += all;
+    }
+    if (threadIdx.x == 0) *total = carry - at;
 }
 
 }  // namespace mcrc_dev

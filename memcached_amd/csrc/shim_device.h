@@ -174,6 +174,9 @@ struct Device {
     DevBuf<uint64_t> sc_goffs, sc_moffs;
     DevBuf<uint32_t> sc_glens, sc_mlens;
     DevBuf<uint8_t> sc_mkind, sc_mikind;
+    // ... with CRC32C_SCRUB_BYTES: a byte stage's bit count and its pinned twin (its masks: rp_mask)
+    DevBuf<unsigned long long> sc_nbits;
+    PinBuf<unsigned long long> sc_hbits;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

@@ -24,11 +24,26 @@
 // (grow-only): 12 B per gap entry (offset and length; the kind is written by
 // the merge), and 14 B per entry of the second list (offset, length and a kind
 // array per repair stage).
+// CRC32C_SCRUB_BYTES (opts->mode): when the item stage of a T repaired nothing,
+// crc32c_repair_bytes' rule runs over the same list, still in sc_list (no
+// second build): item_stages with the mask array, then k_scrub_log_bytes,
+// which expands each repaired entry's mask into one log entry per bit and
+// returns the stage's bit count (8 B cross the link; a host call takes that
+// many flips).  With the bit clear no launch, copy or reservation is added.
+// Scratch (grow-only): 1 B of mask per item-list entry, 8 B of count and its
+// pinned twin, and a host call 8 flip slots per image the stage repaired.
 #pragma once
 
 namespace {
 
-static_assert(CRC32C_SCRUB_BY_HEADER != CRC32C_SCRUB_BY_ITEM, "the log tells the stages apart");
+static_assert(CRC32C_SCRUB_BY_HEADER != CRC32C_SCRUB_BY_ITEM && CRC32C_SCRUB_BY_BYTE != CRC32C_SCRUB_BY_HEADER &&
+                  CRC32C_SCRUB_BY_BYTE != CRC32C_SCRUB_BY_ITEM,
+              "the log tells the stages apart");
+static_assert(!(CRC32C_SCRUB_BYTES & (CRC32C_DEVICE | CRC32C_ASYNC | CRC32C_CFLAGS64 | CRC32C_KEEP_STAMPED |
+                                      CRC32C_LOCATE_ONLY | CRC32C_SCRUB_GAPS)),
+              "a mode bit of its own");
+static_assert(CRC32C_REPAIR_BYTES_SPAN_DEFAULT <= CRC32C_REPAIR_SPAN_DEFAULT,
+              "the byte stage's span limit is at most the item stage's: its work sum too");
 
 struct ScrubRun {
     Device &d;
@@ -40,6 +55,7 @@ struct ScrubRun {
     crc32c_scrub_out *o;  // the caller's arrays
     uint32_t *h32 = nullptr;
     uint64_t *list = nullptr;  // the repair list in use
+    uint64_t items_n = 0;      // the item list's length, of the T whose item stage ran last
     bool gaps = false;         // CRC32C_SCRUB_GAPS
     bool gaps_known = false;   // of the T in hand: ng and, when ng != 0, the second list
     uint64_t ng = 0;
@@ -140,15 +156,53 @@ struct ScrubRun {
             HIP_OK(hipGetLastError());
         }
         if (!dev) {
-            foff.resize(nflips + nrep);
-            fbit.resize(nflips + nrep);
-            fby.resize(nflips + nrep);
-            HIP_OK(hipMemcpyAsync(foff.data() + nflips, fo, nrep * 8, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(fbit.data() + nflips, fb, nrep * 8, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(fby.data() + nflips, fy, nrep, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
+            const int rc = take(fo, fb, fy, nrep);
+            if (rc) return rc;
         }
         nflips += nrep;
+        return CRC32C_OK;
+    }
+
+    // a host call's k flips of one stage, from its scratch to the host's log behind nflips
+    int take(const uint64_t *fo, const uint64_t *fb, const uint8_t *fy, uint64_t k) {
+        foff.resize(nflips + k);
+        fbit.resize(nflips + k);
+        fby.resize(nflips + k);
+        HIP_OK(hipMemcpyAsync(foff.data() + nflips, fo, k * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(fbit.data() + nflips, fb, k * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(fby.data() + nflips, fy, k, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return CRC32C_OK;
+    }
+
+    // a byte stage's flips behind the log's nflips, one per set bit of each
+    // of its nrep masks: at most 8 nrep, the exact count comes back from the kernel
+    int log_bytes(const uint8_t *ok, const uint64_t *byte, const uint8_t *mask, uint64_t n, uint64_t nrep) {
+        uint64_t *fo = o->flip_offsets, *fb = o->flip_bits;
+        uint8_t *fy = o->flip_by;
+        uint64_t at = nflips, cap = o->flip_cap;
+        unsigned long long *nbits = d.sc_nbits.reserve(8), *h = d.sc_hbits.reserve(8);
+        if (!nbits || !h) return CRC32C_ENOMEM;
+        if (!dev) {
+            fo = d.sc_foff.reserve(8 * nrep * 8);
+            fb = d.sc_fbit.reserve(8 * nrep * 8);
+            fy = d.sc_fby.reserve(8 * nrep);
+            if (!fo || !fb || !fy) return CRC32C_ENOMEM;
+            at = 0;
+            cap = 8 * nrep;
+        }
+        hipLaunchKernelGGL(mcrc_dev::k_scrub_log_bytes, dim3(1), dim3(mcrc_dev::kScrubLogThreads), 0, st,
+                           (const uint64_t *)list, ok, byte, mask, n, (uint32_t)CRC32C_SCRUB_BY_BYTE, at, cap, fo, fb,
+                           fy, nbits);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(h, nbits, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        const uint64_t k = *h;
+        if (!dev) {
+            const int rc = take(fo, fb, fy, k);
+            if (rc) return rc;
+        }
+        nflips += k;
         return CRC32C_OK;
     }
 
@@ -160,6 +214,7 @@ struct ScrubRun {
         if (rc) return rc;
         *status = CRC32C_OK;
         *nrep = 0;
+        if (ITEMS) items_n = n;
         if (n == 0) return CRC32C_OK;
         mcrc_dev::SpanArgs a = item_args(d, page, base_bytes, wbuf_bytes, n, flags);
         a.offsets = list;
@@ -198,6 +253,34 @@ struct ScrubRun {
         if (*nrep) rc = log(ok, bit, n, *nrep, ITEMS ? CRC32C_SCRUB_BY_ITEM : CRC32C_SCRUB_BY_HEADER);
         return rc;
     }
+
+    // crc32c_repair_bytes' rule over the list the item stage of this T just
+    // ran on (list, items_n: nothing was built since); bspan: the resolved limit
+    int repair_bytes(uint32_t bspan, int *status, uint64_t *nrep) {
+        const uint64_t n = items_n;
+        *status = CRC32C_OK;
+        *nrep = 0;
+        if (n == 0) return CRC32C_OK;
+        mcrc_dev::SpanArgs a = item_args(d, page, base_bytes, wbuf_bytes, n, flags);
+        a.offsets = list;
+        // (the item stage's route: it took this list)
+        const mcrc::ItemRoute route = mcrc::item_route(n, base_bytes, small_max(), false);
+        uint8_t *ok = d.rp_ok.reserve(n), *mask = d.rp_mask.reserve(n);
+        uint64_t *byte = d.rp_bit.reserve(n * 8);
+        if (!ok || !byte || !mask) return CRC32C_ENOMEM;
+        unsigned long long *h = nullptr;
+        bool searched = false;
+        int rc = item_stages(d, st, a, base_bytes, n, route, bspan, ok, byte, false, &h, &searched, mask);
+        if (rc == CRC32C_EWORK) {
+            *status = rc;
+            return CRC32C_OK;
+        }
+        if (rc) return rc;
+        HIP_OK(hipStreamSynchronize(st));
+        *nrep = h[mcrc_dev::kRpRepaired];
+        if (*nrep) rc = log_bytes(ok, byte, mask, n, *nrep);
+        return rc;
+    }
 };
 
 int scrub_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, const crc32c_scrub_opts *opts,
@@ -217,6 +300,9 @@ int scrub_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, const crc3
     const uint64_t nw = (base_bytes + wbuf_bytes - 1) / wbuf_bytes;
     if (nw >= 0x7fffffffull) return CRC32C_EINVAL;
     const uint32_t max_rounds = op.max_rounds ? op.max_rounds : CRC32C_SCRUB_ROUNDS_DEFAULT;
+    const bool bytes = op.mode & CRC32C_SCRUB_BYTES;
+    const uint32_t bspan = op.max_span ? std::min<uint32_t>(op.max_span, CRC32C_REPAIR_BYTES_SPAN_DEFAULT)
+                                       : CRC32C_REPAIR_BYTES_SPAN_DEFAULT;
 
     PageLists t;
     uint64_t headers_repaired = 0, items_repaired = 0, nflips = 0;
@@ -264,6 +350,10 @@ int scrub_pages(void *base, uint64_t base_bytes, uint64_t wbuf_bytes, const crc3
         if (nrep == 0) {  // (headers before items, every time)
             if ((rc = r.repair<true>(t, op.max_span, &status, &nrep))) return rc;
             if (status != CRC32C_OK) break;
+            if (nrep == 0 && bytes) {  // (the same list, the byte rule)
+                if ((rc = r.repair_bytes(bspan, &status, &nrep))) return rc;
+                if (status != CRC32C_OK) break;
+            }
             if (nrep == 0) {
                 complete = 1;  // (T describes the page: no further triage)
                 break;
