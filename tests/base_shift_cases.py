@@ -113,7 +113,9 @@ def batch_parts():
 
 
 # (0: no span kernel runs and k_final must not take the caller's out[] for a kernel's result)
-SHARED_LENS = (0, 1, 100, 1009, 1024, 4133, 4225, 8195)
+# (257..513: across kWholeMax = 512.  len + 127 <= 512 is k_final alone, and from 386 to 512 a span is its
+# thread's or the span kernel's by its own alignment: one batch holds both)
+SHARED_LENS = (0, 1, 100, 257, 384, 385, 386, 400, 448, 511, 512, 513, 1009, 1024, 4133, 4225, 8195)
 
 
 @functools.lru_cache(maxsize=None)

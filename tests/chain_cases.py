@@ -148,6 +148,12 @@ def route_cases() -> list[Case]:
         buf = rng.integers(0, 256, size, dtype=np.uint8)
         cases.append(Case(f"fixed{length}_{route}", buf, _pattern_first(n), n, offsets=offs, length=length,
                           small_max=0, route=route))
+    # the same two kernels taking the iovs by stride (k_lines<0, false>, k_blocks<true, false>): the extstore
+    # image shape, a span at +32 of every 4165-byte image, and 4097-byte iovs that overlap by a byte
+    for length, stride, route in ((4133, 4165, "k5"), (4097, 4096, "id_blocks")):
+        buf = rng.integers(0, 256, (n - 1) * stride + length, dtype=np.uint8)
+        cases.append(Case(f"fixed{length}_{route}_stride", buf, _pattern_first(n), n, stride=stride, length=length,
+                          small_max=0, route=route))
     return cases
 
 

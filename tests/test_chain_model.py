@@ -89,7 +89,12 @@ def test_zero_cases_hold_what_they_promise():
 def test_route_and_digit_cases_have_their_shapes():
     by_name = {c.name: c for c in cc.route_cases()}
     assert set(by_name) == {"lens_small", "lens_planned", "fixed4096_k1", "fixed4133_k5", "fixed4090_id_blocks",
-                            "fixed9000_id_spans", "fixed100_id_final"}
+                            "fixed9000_id_spans", "fixed100_id_final", "fixed4133_k5_stride",
+                            "fixed4097_id_blocks_stride"}
+    for name in ("fixed4133_k5_stride", "fixed4097_id_blocks_stride"):
+        c = by_name[name]
+        assert c.offsets is None and c.lens is None and c.small_max == 0
+        assert c.buf.size == (c.n - 1) * c.stride + c.length  # (the smallest buffer the library accepts)
     for c in by_name.values():
         counts = set(np.diff(c.first.astype(np.int64)).tolist())
         assert counts == {0, 1, 2, 7}, c.name

@@ -1014,13 +1014,18 @@ def test_offsets_with_fixed_length(torch):
     np.testing.assert_array_equal(outh, oracle.batch(host, offs, np.full(n, L)))
 
 
-@pytest.mark.parametrize("L", [1, 15, 100, 896, 897, 898, 1008, 1009, 1010, 1024, 1040, 4080, 4097, 4200, 4209, 4224,
-                               4225, 4240, 5104, 5125, 8195, 65536, 65552])
+@pytest.mark.parametrize("L", [1, 15, 100, 257, 384, 385, 386, 400, 448, 511, 512, 513, 896, 897, 898, 1008, 1009, 1010,
+                               1024, 1040, 4080, 4097, 4200, 4209, 4224, 4225, 4240, 5104, 5125, 8195, 65536, 65552])
 def test_fixed_length_head_fragment_thresholds(torch, L):
     """offsets[] with one shared length (one unit per span, no plan) at the
     lengths where the head fragment moves between the span kernel and the
-    span's thread (kFragMax = 128; whole spans up to kWholeMax = 1024) or the
-    span skips the kernel entirely."""
+    span's thread (kFragMax = 128; whole spans up to kWholeMax = 512) or the
+    span skips the kernel entirely.  257..513 lie across kWholeMax: up to 385
+    (len + 127 <= 512) no span kernel runs, k_final folds every span; from 386
+    to 512 a span is its thread's when vlen = len + its pad to the 128-byte
+    grid is at most 512, so the random offsets of one batch mix whole spans
+    with kernel spans; at 513 none is whole.  (The lengths around 896..1040
+    were the same boundary when kWholeMax was 1024.)"""
     import ctypes
     rng = np.random.default_rng(L)
     n = 700

@@ -60,6 +60,63 @@ def test_chain_cases_take_the_routes_they_name(exe):
     assert {c.route for c in cases} == {"k1", "small", "k5", "id_blocks", "id_spans", "id_final", "planned"}
 
 
+def _route(exe, n, length, stride, has_lens, base_mod, base_bytes, small_max):
+    """span_route's answer for a batch without offsets[], by the program's `route` mode."""
+    args = [n, length, stride, 0, int(has_lens), base_mod, base_bytes, 8192 if small_max is None else small_max]
+    r = subprocess.run([exe, "route"] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, (args, r.stdout, r.stderr)
+    return r.stdout.strip()
+
+
+def test_stride_cases_take_the_routes_they_name(exe):
+    """tests/stride_cases.py labels every fixed-stride case with its span route:
+    span_route's own answer for each, at the three base residues
+    tests/test_gpu_strides.py places it at (no case has K1's shape, so the base
+    decides nothing).  And the 2^31 line: 4096-byte spans at a stride of
+    2^31 - 16 are K1's, at 2^31 k_blocks'."""
+    from tests import stride_cases as sc
+    for c in sc.cases():
+        for base_mod in (0, 1, 127):
+            got = _route(exe, c.n, c.length, c.stride, c.lens is not None, base_mod, c.nbytes, c.small_max)
+            assert got == c.route, (c.name, base_mod, got)
+    assert {c.route for c in sc.cases()} == set(sc.ROUTES) == {"small", "k5", "id_blocks", "id_spans", "id_final",
+                                                                "planned"}
+    # every length and size the cases are there for
+    have = {(c.route, c.length) for c in sc.cases() if c.lens is None}
+    assert {(r, L) for r, (lengths, _) in sc.FIXED.items() for L in lengths} <= have
+    assert {c.n for c in sc.cases() if c.route == "k5"} >= {1, 63, 64, 65, 131, 8193}
+    assert any(c.length == 4096 and c.stride % 16 for c in sc.cases() if c.route == "id_blocks")
+    assert {(c.route, c.stride >= int(c.lens.max())) for c in sc.cases() if c.lens is not None} == {
+        ("planned", True), ("planned", False), ("small", False)}
+    assert {c.route for c in sc.cases() if c.host} == set(sc.ROUTES)
+    for length, stride, route in sc.LINE_CASES:
+        size = (sc.LINE_N - 1) * stride + length
+        assert _route(exe, sc.LINE_N, length, stride, False, 0, size, 0) == route, (length, stride)
+        assert (sc.LINE_N - 1) * stride >= 1 << 32 or route == "k1"
+    assert ((4096, sc.LINE - 16, "k1") in sc.LINE_CASES and (4096, sc.LINE, "id_blocks") in sc.LINE_CASES)
+
+
+def test_stride_case_buffers_are_the_smallest_accepted(exe):
+    """Every case's buffer is exactly (n - 1) * stride + len bytes: with one
+    byte less fixed_spans_fit refuses the descriptor (span_route: invalid, which
+    crc32c_batch returns as CRC32C_EINVAL).  With lens[] the spans are checked
+    on the device, and the buffer ends where the last span does."""
+    from tests import stride_cases as sc
+    for c in sc.cases():
+        assert c.buf.size == c.nbytes
+        if c.lens is None:
+            assert c.nbytes == (c.n - 1) * c.stride + c.length
+            if c.nbytes:
+                got = _route(exe, c.n, c.length, c.stride, False, 0, c.nbytes - 1, c.small_max)
+                assert got == "invalid", (c.name, got)
+        else:
+            ends = c.offsets().astype(np.int64) + c.lens.astype(np.int64)
+            assert c.nbytes == ends.max() and c.length == sc.DECOY_LEN
+    for length, stride, _ in sc.LINE_CASES:
+        size = (sc.LINE_N - 1) * stride + length
+        assert _route(exe, sc.LINE_N, length, stride, False, 0, size - 1, 0) == "invalid"
+
+
 @pytest.mark.parametrize("parts", range(1, 9))
 def test_shard_cuts_match_plan(exe, parts):
     """crc32c_shard_cuts' body against memcached_amd/shard.py plan() on the
