@@ -1009,6 +1009,80 @@ typedef struct crc32c_job *crc32c_job_t;
 int crc32c_batch_submit(const crc32c_spans *spans, unsigned flags, crc32c_job_t *job);
 int crc32c_batch_wait(crc32c_job_t job);
 
+/* A batch of byte spans that lie wherever the caller's buffers do: one pointer
+ * per span, no common base.  The read path's shape (storage.c:147-178,
+ * proxy_internal.c:16-60): slab pages malloc'ed one by one (slabs.c:613-616),
+ * the proxy's malloc(ntotal) per read (proxy_internal.c:91), one iov per chunk
+ * of a chunked item (storage.c:298-337).
+ *   span i = [ptrs[i], + (lens ? lens[i] : len))
+ *   out[i] = crc32c(crc_in ? crc_in[i] : 0, span i), bit-identical to the
+ *   reference.  Spans may repeat, overlap and come in any order.  A span of no
+ *   bytes gives out[i] = crc_in[i] (0 without crc_in); its pointer may be NULL
+ *   and is never dereferenced.
+ * What is read.  There is no bound to check the spans against, so the contract
+ * is what the call reads:
+ *   pageable host memory        the span's own bytes [ptrs[i], + len_i), by the
+ *                               host, and nothing else;
+ *   device and page-locked      the 16-byte granules (addresses that are
+ *   memory                      multiples of 16) that the span's bytes touch.
+ *                               A granule never crosses a page, so any span
+ *                               inside mapped memory is safe.
+ * Host batches (no CRC32C_DEVICE).  A NULL pointer with len_i != 0, or a span
+ * longer than crc32c_batch's host limit (256 MiB - 16): CRC32C_EINVAL, nothing
+ * read, out untouched.  When every span lies in page-locked memory
+ * (crc32c_host_alloc, crc32c_host_register, or locked by other means), the
+ * spans are at most 256 KiB and the batch is small (at most 8192 spans, and
+ * their lengths add up to at most 8 MiB -- or, with lens == NULL, len is at most
+ * 1 MiB: buffers that lie far apart do not make a batch large), the GPU reads
+ * the spans where they lie, in one launch shared with other threads' jobs (the
+ * queue of crc32c_batch_submit).  Any other batch is packed: the host copies
+ * each span's bytes, and only those, back to back into the pipeline's pinned
+ * slots (each span keeps its address mod 16), while the slot before is
+ * checksummed.  A slot whose spans are all page-locked and average 64 KiB or
+ * more is filled by one DMA per span instead, without the host copy.
+ * Device batches (CRC32C_DEVICE).  ptrs, lens, crc_in and out are device
+ * arrays; every ptrs[i] is memory of the current device, from any allocation.
+ * A span longer than CRC32C_MAX_SPAN is not read: out[i] = 0 and the call
+ * returns CRC32C_ERANGE, as crc32c_batch treats it (lens == NULL with such a
+ * len: CRC32C_EINVAL).  Unless the batch is small by n and a fixed len, one
+ * pass over ptrs and lens first finds the spans' extent and the sum of their
+ * lengths (24 bytes read back, 8 B of grow-only scratch per span), which decide
+ * the route as base_bytes decides crc32c_batch's.  With CRC32C_ASYNC the call
+ * still returns without waiting for the CRC kernels; it waits for that
+ * read-back only.
+ * No device: CRC32C_ENODEV, nothing written.  n == 0: CRC32C_OK. */
+typedef struct crc32c_ptr_batch {
+    const void *const *ptrs;  /* n span starts */
+    const uint32_t *lens;     /* n lengths, or NULL: every span is `len` bytes */
+    uint32_t len;
+    const uint32_t *crc_in;   /* or NULL (0) */
+    uint32_t *out;            /* n */
+    uint64_t n;
+} crc32c_ptr_batch;
+
+typedef struct crc32c_ptr_opts { /* NULL: all zero */
+    uint32_t mode;            /* CRC32C_DEVICE | CRC32C_ASYNC; others ignored */
+    void *stream;
+} crc32c_ptr_opts;
+
+int crc32c_batch_ptrs(const crc32c_ptr_batch *b, const crc32c_ptr_opts *opts);
+
+/* Asynchronous form, as crc32c_batch_submit is crc32c_batch's: wait with
+ * crc32c_batch_wait.  The spans are translated when the job is submitted.  A
+ * host job whose spans are all page-locked and at most 256 KiB, with at most
+ * 8192 of them, shares the queue's launches with every other coalescable job
+ * (crc32c_queue_stats counts it among them); any other runs alone on the
+ * dispatcher, a CRC32C_DEVICE job behind the submitter's default stream.
+ * opts->stream is not used. */
+int crc32c_ptrs_submit(const crc32c_ptr_batch *b, const crc32c_ptr_opts *opts, crc32c_job_t *job);
+
+/* crc32c_batch_chains over such iovs: the same fold, the same chain_first
+ * rules (a host one that descends or passes iovs->n: CRC32C_EINVAL), iovs->out
+ * receives each iov's own CRC, iovs->crc_in must be NULL.  nchains == 0:
+ * CRC32C_OK, nothing written. */
+int crc32c_chains_ptrs(const crc32c_ptr_batch *iovs, const uint64_t *chain_first, uint64_t nchains,
+                       uint32_t *out, const crc32c_ptr_opts *opts);
+
 /* Queue counters of the current device since the first submit: coalesced
  * kernel launches, the spans and jobs they carried, and jobs run alone.  Any
  * pointer may be NULL. */
@@ -1024,7 +1098,11 @@ void crc32c_host_free(void *p);
 
 /* Page-lock and map an existing host range (e.g. the slab arena that read
  * buffers come from, storage.c:264-337) so host batches over it are read by
- * the GPU in place: coalesced by the queue and copied without staging. */
+ * the GPU in place: coalesced by the queue and copied without staging.  The
+ * ranges need not be one arena: register each slab page where it is malloc'ed
+ * (slabs.c:613-616) and name the buffers by pointer (crc32c_batch_ptrs).  The
+ * library records every range it page-locks, so a span's device address is a
+ * lookup, not a runtime call. */
 int crc32c_host_register(void *p, size_t bytes);
 int crc32c_host_unregister(void *p);
 

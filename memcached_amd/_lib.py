@@ -61,7 +61,7 @@ EXPORTED = (
     "crc32c_set_small_max", "crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages",
     "crc32c_set_k1_tail_min", "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit",
     "crc32c_repair_headers", "crc32c_triage_pages", "crc32c_scrub_pages", "crc32c_repair_bytes",
-    "crc32c_locate_byte",
+    "crc32c_locate_byte", "crc32c_batch_ptrs", "crc32c_ptrs_submit", "crc32c_chains_ptrs",
 )
 
 
@@ -141,6 +141,26 @@ class BytesOut(ctypes.Structure):
     ]
 
 
+class PtrBatch(ctypes.Structure):
+    """crc32c_ptr_batch"""
+    _fields_ = [
+        ("ptrs", ctypes.c_void_p),
+        ("lens", ctypes.c_void_p),
+        ("len", ctypes.c_uint32),
+        ("crc_in", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("n", ctypes.c_uint64),
+    ]
+
+
+class PtrOpts(ctypes.Structure):
+    """crc32c_ptr_opts"""
+    _fields_ = [
+        ("mode", ctypes.c_uint32),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
 _INT, _UINT, _U32, _U64 = ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, ctypes.c_uint64
 _SIZE, _PTR, _SPANS, _U64P = ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(Spans), ctypes.POINTER(ctypes.c_uint64)
 _SCALAR = (_U32, [_U32, _PTR, _SIZE])  # crc_func of include/crc32c.h
@@ -174,6 +194,9 @@ PROTOTYPES = {
     "crc32c_repair_bytes": (_INT, [_PTR, _U64, _U64, _PTR, _U64, ctypes.POINTER(BytesOpts), ctypes.POINTER(BytesOut)]),
     "crc32c_locate_byte": (_U64, [_U32, _U32, _U64, ctypes.POINTER(ctypes.c_uint8)]),
     "crc32c_batch_chains": (_INT, [_SPANS, _PTR, _U64, _PTR, _UINT, _PTR]),
+    "crc32c_batch_ptrs": (_INT, [ctypes.POINTER(PtrBatch), ctypes.POINTER(PtrOpts)]),
+    "crc32c_ptrs_submit": (_INT, [ctypes.POINTER(PtrBatch), ctypes.POINTER(PtrOpts), ctypes.POINTER(_PTR)]),
+    "crc32c_chains_ptrs": (_INT, [ctypes.POINTER(PtrBatch), _PTR, _U64, _PTR, ctypes.POINTER(PtrOpts)]),
     "crc32c_host_alloc": (_PTR, [_SIZE]),
     "crc32c_host_free": (None, [_PTR]),
     "crc32c_batch_submit": (_INT, [_SPANS, _UINT, ctypes.POINTER(_PTR)]),
@@ -190,7 +213,8 @@ PROTOTYPES = {
 # what an older build loaded through MCRC_LIB (an A/B of two builds) may lack
 NEWER = ("crc32c_stamp_pages", "crc32c_copy_items", "crc32c_salvage_pages", "crc32c_set_k1_tail_min",
          "crc32c_recover_pages", "crc32c_repair_items", "crc32c_locate_bit", "crc32c_repair_headers",
-         "crc32c_triage_pages", "crc32c_scrub_pages", "crc32c_repair_bytes", "crc32c_locate_byte")
+         "crc32c_triage_pages", "crc32c_scrub_pages", "crc32c_repair_bytes", "crc32c_locate_byte",
+         "crc32c_batch_ptrs", "crc32c_ptrs_submit", "crc32c_chains_ptrs")
 
 
 def _load():

@@ -39,8 +39,8 @@ from . import _lib
 from ._lib import (CRC32C_ASYNC, CRC32C_CFLAGS64, CRC32C_DEVICE, CRC32C_KEEP_STAMPED, CRC32C_SCRUB_BY_BYTE,
                    CRC32C_SCRUB_BYTES, CRC32C_SCRUB_GAPS, Crc32cError, check, lib)
 
-# (recover_pages, triage_pages, repair_items, locate_bit, repair_headers, scrub_pages, repair_bytes and locate_byte are
-# public as well; tests/test_python_face.py pins this list as it stood before them)
+# (recover_pages, triage_pages, repair_items, locate_bit, repair_headers, scrub_pages, repair_bytes, locate_byte,
+# batch_ptrs and chains_ptrs are public as well; tests/test_python_face.py pins this list as it stood before them)
 __all__ = ["crc32c", "crc32c_sw", "batch", "verify_items", "stamp_items", "stamp_pages", "verify_pages", "batch_chains",
            "copy_items", "salvage_pages",
            "batch_multi",
@@ -705,6 +705,57 @@ def batch_chains(buf, offsets, lens, chain_first, stream=None):
     out = side.empty(nchains, _U32)
     check(lib.crc32c_batch_chains(ctypes.byref(s), _ptr(chain_first), nchains, _ptr(out), side.flag, side.stream),
           "crc32c_batch_chains")
+    return out
+
+
+def _ptr_batch(buffers, crc_in, stream):
+    """(side, crc32c_ptr_batch, out) of a list of buffers: device tensors (all
+    of them: a device batch, its descriptors built on their device) or host
+    data (numpy arrays, bytes: read where they lie)."""
+    buffers = list(buffers)
+    n = len(buffers)
+    if any(_is_dev(b) for b in buffers):
+        if not all(_is_dev(b) for b in buffers):
+            raise ValueError("buffers: device tensors and host data in one batch")
+        side = _Device(buffers[0], stream)
+    else:
+        side = _HOST
+    bufs = [side.buffer(b, f"buffers[{i}]") for i, b in enumerate(buffers)]
+    ptrs = np.array([_ptr(b) if nb else 0 for b, nb in bufs], np.uint64)
+    lens = np.array([nb for _, nb in bufs], np.uint32)
+    if side.dev:  # the descriptors of a device batch are device arrays
+        ptrs = side.torch.from_numpy(ptrs.view(np.int64)).to(side.device)
+        lens = side.torch.from_numpy(lens.view(np.int32)).to(side.device)
+    crc_in = side.desc(crc_in, "crc_in", _U32, n)
+    out = side.empty(n, _U32)
+    b = _lib.PtrBatch(_ptr(ptrs), _ptr(lens), 0, _ptr(crc_in), _ptr(out), n)
+    b.arrays = bufs, ptrs, lens, crc_in  # (bare addresses: the converted copies live as long as the struct)
+    return side, b, out
+
+
+def batch_ptrs(buffers, crc_in=None, stream=None):
+    """crc32c_batch_ptrs: the CRC-32C of each of ``buffers`` -- a list of numpy
+    arrays or bytes wherever they lie (page-locked ones are read in place, the
+    others' bytes are packed), or a list of device tensors from any
+    allocations.  Returns uint32 CRCs, one per buffer; crc_in[i] starts the
+    i-th (default 0)."""
+    side, b, out = _ptr_batch(buffers, crc_in, stream)
+    opts = _lib.PtrOpts(side.flag, side.stream)
+    check(lib.crc32c_batch_ptrs(ctypes.byref(b), ctypes.byref(opts)), "crc32c_batch_ptrs")
+    return out
+
+
+def chains_ptrs(buffers, chain_first, stream=None):
+    """crc32c_chains_ptrs: batch_chains over iovs given as a list of buffers
+    (as for batch_ptrs): chain c covers buffers [chain_first[c],
+    chain_first[c+1])."""
+    side, b, _iov_out = _ptr_batch(buffers, None, stream)
+    nchains = len(chain_first) - 1
+    chain_first = side.desc(chain_first, "chain_first", _U64, nchains + 1)
+    out = side.empty(nchains, _U32)
+    opts = _lib.PtrOpts(side.flag, side.stream)
+    check(lib.crc32c_chains_ptrs(ctypes.byref(b), _ptr(chain_first), nchains, _ptr(out), ctypes.byref(opts)),
+          "crc32c_chains_ptrs")
     return out
 
 

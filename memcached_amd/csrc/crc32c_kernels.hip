@@ -45,3 +45,4 @@
 #include "k_header.h"  // crc32c_repair_headers: k_header_variants, k_header_apply
 #include "k_scrub.h"   // crc32c_scrub_pages: k_scrub_headers, k_scrub_items, k_scrub_gaps, k_scrub_gap_merge, k_scrub_log, k_scrub_log_bytes
 #include "k_repair_bytes.h"  // crc32c_repair_bytes: k_repair_bytes_search, k_repair_bytes_apply
+#include "k_ptrs.h"    // crc32c_batch_ptrs on device arrays: k_ptr_rebase

@@ -57,6 +57,7 @@ uint32_t crc32c_sw_big(uint32_t crc, void const *buf, size_t len) { return mcrc:
 #include "shim_launch.h"
 #include "shim_host.h"
 #include "shim_queue.h"
+#include "shim_ptrs.h"
 #include "shim_walk.h"
 #include "shim_salvage.h"
 #include "shim_triage.h"
@@ -79,21 +80,29 @@ void *crc32c_host_alloc(size_t bytes) {
     if (bytes == 0 || crc32c_gpu_count() <= 0) return nullptr;
     void *p = nullptr;
     // portable: usable by every device's copy engine (crc32c_batch_multi)
-    return hipHostMalloc(&p, bytes, hipHostMallocPortable) == hipSuccess ? p : nullptr;
+    if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) return nullptr;
+    pin_record(p, bytes);
+    return p;
 }
 
-void crc32c_host_free(void *p) { if (p) (void)hipHostFree(p); }
+void crc32c_host_free(void *p) {
+    if (!p) return;
+    pin_forget(p);
+    (void)hipHostFree(p);
+}
 
 int crc32c_host_register(void *p, size_t bytes) {
     if (!p || !bytes) return CRC32C_EINVAL;
     if (crc32c_gpu_count() <= 0) return CRC32C_ENODEV;
     HIP_OK(hipHostRegister(p, bytes, hipHostRegisterMapped | hipHostRegisterPortable));
+    pin_record(p, bytes);
     return CRC32C_OK;
 }
 
 int crc32c_host_unregister(void *p) {
     if (!p) return CRC32C_EINVAL;
     if (crc32c_gpu_count() <= 0) return CRC32C_ENODEV;
+    pin_forget(p);
     HIP_OK(hipHostUnregister(p));
     return CRC32C_OK;
 }
@@ -195,35 +204,35 @@ int crc32c_batch_chains(const crc32c_spans *iovs, const uint64_t *chain_first, u
     std::lock_guard<std::mutex> lk(d->mu);
     hipStream_t st = dev ? (hipStream_t)stream : d->stream;
     Lease lease(*d, st);
-    const uint32_t *crcs = iovs->out, *lens = iovs->lens;
-    const uint64_t *first = chain_first;
-    uint32_t *dout = out;
     Count nrange = nullptr;
     if (dev) {
         if (!device_range_ok(iovs->base, iovs->base_bytes)) return CRC32C_EINVAL;
         rc = run_spans(*d, *iovs, mcrc::span_route(*iovs, small_max()), st, (flags & CRC32C_ASYNC) ? nullptr : &nrange);
         if (rc) return rc;
-    } else {  // stage the fold's inputs
-        const uint64_t n = iovs->n;
-        uint8_t *buf = d->stage.reserve(mcrc::chain_stage_bytes(n, nchains));
-        if (!buf) return CRC32C_ENOMEM;
-        uint32_t *c_d = (uint32_t *)buf, *l_d = lens ? c_d + n : nullptr;
-        uint64_t *f_d = (uint64_t *)(buf + mcrc::chain_first_off(n));
-        HIP_OK(hipMemcpyAsync(c_d, iovs->out, n * 4, hipMemcpyHostToDevice, st));
-        if (lens) HIP_OK(hipMemcpyAsync(l_d, lens, n * 4, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(f_d, chain_first, (nchains + 1) * 8, hipMemcpyHostToDevice, st));
-        crcs = c_d;
-        lens = l_d;
-        first = f_d;
-        dout = (uint32_t *)(f_d + nchains + 1);
     }
-    const int g = (int)std::min<uint64_t>((nchains + 255) / 256, 4096);
-    hipLaunchKernelGGL(mcrc_dev::k_chain, dim3(g), dim3(256), 0, st, crcs, lens, iovs->len, first, nchains, dout,
-                       (const uint32_t *)d->xpow);
-    HIP_OK(hipGetLastError());
-    if (!dev) HIP_OK(hipMemcpyAsync(out, dout, nchains * 4, hipMemcpyDeviceToHost, st));
-    if (!dev || !(flags & CRC32C_ASYNC)) HIP_OK(hipStreamSynchronize(st));
-    return nrange && *nrange ? CRC32C_ERANGE : CRC32C_OK;
+    return fold_chains(*d, iovs->out, iovs->lens, iovs->len, iovs->n, chain_first, nchains, out, dev, flags, st, nrange);
+}
+
+int crc32c_batch_ptrs(const crc32c_ptr_batch *b, const crc32c_ptr_opts *opts) {
+    if (!b) return CRC32C_EINVAL;
+    return batch_ptrs(*b, opts ? opts->mode : 0u, opts ? (hipStream_t)opts->stream : nullptr);
+}
+
+int crc32c_ptrs_submit(const crc32c_ptr_batch *b, const crc32c_ptr_opts *opts, crc32c_job_t *job) {
+    if (!b || !job) return CRC32C_EINVAL;
+    crc32c_job *j = nullptr;
+    int rc = make_ptr_job(*b, opts ? opts->mode : 0u, &j);
+    if (rc || (rc = submit_or_free(j))) return rc;
+    *job = j;
+    return CRC32C_OK;
+}
+
+int crc32c_chains_ptrs(const crc32c_ptr_batch *iovs, const uint64_t *chain_first, uint64_t nchains, uint32_t *out,
+                       const crc32c_ptr_opts *opts) {
+    if (!iovs || !chain_first || (nchains && !out) || iovs->crc_in) return CRC32C_EINVAL;
+    if (nchains == 0) return CRC32C_OK;
+    return chains_ptrs(*iovs, chain_first, nchains, out, opts ? opts->mode : 0u,
+                       opts ? (hipStream_t)opts->stream : nullptr);
 }
 
 // (Stamp calls before verify calls: the kernel templates are laid out in the

@@ -1,12 +1,17 @@
 // host_route.h -- every decision of the host shim that needs no GPU: where a
-// batch goes (span_route, item_route), the launch geometry, the host
-// pipeline's order and chunk cuts, the shard cuts.  Plain C++ over k_consts.h;
-// tests/integration/host_route_check.cpp runs it on the CPU.
+// batch goes (span_route, item_route, ptr_route), the launch geometry, the host
+// pipeline's order and chunk cuts, a pointer batch's pack plan, the registry of
+// page-locked ranges, the shard cuts.  Plain C++ over k_consts.h;
+// tests/integration/host_route_check.cpp and ptr_pack_check.cpp run it on the CPU.
 #pragma once
 
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <shared_mutex>
 #include <vector>
 
 #include "../../include/crc32c_batch.h"
@@ -190,6 +195,113 @@ static inline Chunk next_chunk(const crc32c_spans &s, const std::vector<uint64_t
     }
     return {k1, lo, hi};
 }
+
+// Pointer batches (crc32c_ptr_batch): spans with no common base.
+static inline uint64_t ptr_len(const crc32c_ptr_batch &b, uint64_t i) { return b.lens ? b.lens[i] : b.len; }
+
+// Where a pointer batch goes.  small: one k_small launch over the spans where
+// they lie (a host batch: through the queue, when its spans are short enough
+// for it); spans: a host batch is packed into the pipeline's slots, a device
+// batch runs as the offsets batch its rebase makes (span_route without the
+// small rule).  Small is span_route's rule with the sum of the lengths in
+// place of base_bytes: what a group reads is bounded by it, however far apart
+// the buffers lie.  sum_len: the lengths' sum (with lens); visible: every span
+// is device-visible (a device batch: true).
+enum class PtrRoute { empty, invalid, small, spans };
+static inline PtrRoute ptr_route(uint64_t n, bool has_lens, uint32_t len, uint64_t sum_len, bool visible,
+                                 uint64_t small_max) {
+    if (n == 0) return PtrRoute::empty;
+    if (!has_lens && len > dev::kMaxSpan) return PtrRoute::invalid;
+    if (!visible) return PtrRoute::spans;
+    if (n <= small_max && (has_lens ? sum_len <= kSmallBaseMax : len <= kSmallSpanMax)) return PtrRoute::small;
+    return n >= kCountMax ? PtrRoute::invalid : PtrRoute::spans;
+}
+// The span route of a rebased device pointer batch s (offsets given: never K1).
+static inline SpanRoute ptr_span_route(const crc32c_spans &s, uint64_t sum_len, uint64_t small_max) {
+    switch (ptr_route(s.n, s.lens != nullptr, s.len, sum_len, true, small_max)) {
+        case PtrRoute::empty: return SpanRoute::empty;
+        case PtrRoute::invalid: return SpanRoute::invalid;
+        case PtrRoute::small: return SpanRoute::small;
+        default: return span_route(s, 0);
+    }
+}
+
+// A host pointer batch can be staged: no NULL span that has bytes, none longer
+// than a pipeline slot takes.
+static inline bool ptr_spans_ok(const crc32c_ptr_batch &b, uint64_t slot_bytes = kSlotBytes) {
+    for (uint64_t i = 0; i < b.n; ++i) {
+        const uint64_t len = ptr_len(b, i);
+        if ((len && !b.ptrs[i]) || len > slot_bytes - 16) return false;
+    }
+    return true;
+}
+
+// The pack plan: the next chunk of a packed pointer batch, spans [k0, k1) in
+// caller order (chains fold in it), pos[k - k0] the slot position of span k.
+// A span keeps its address mod 16, so the kernels meet the piece splits they
+// would meet in place, and owns every 16-byte granule its bytes touch: the
+// next span starts on the granule behind them.  A span of no bytes takes no
+// room.  The chunk ends before the span that would pass slot_bytes (a multiple
+// of 16) or slot_items; bytes: the slot's bytes in use (a multiple of 16).
+struct PackChunk {
+    uint64_t k1, bytes;
+};
+static inline PackChunk pack_chunk(const crc32c_ptr_batch &b, uint64_t k0, uint64_t *pos,
+                                   uint64_t slot_bytes = kSlotBytes, uint64_t slot_items = kSlotItems) {
+    uint64_t k1 = k0, cur = 0;
+    for (; k1 < b.n && k1 - k0 < slot_items; ++k1) {
+        const uint64_t len = ptr_len(b, k1), at = len ? cur + ((uintptr_t)b.ptrs[k1] & 15u) : cur;
+        const uint64_t end = len ? (at + len + 15) & ~15ull : cur;
+        if (end > slot_bytes) break;
+        pos[k1 - k0] = at;
+        cur = end;
+    }
+    return {k1, cur};
+}
+// The chunk's bytes copied into its slot: the spans' own bytes and no others.
+static inline void pack_copy(const crc32c_ptr_batch &b, uint64_t k0, uint64_t k1, const uint64_t *pos, uint8_t *slot) {
+    for (uint64_t k = k0; k < k1; ++k)
+        if (const uint64_t len = ptr_len(b, k)) memcpy(slot + pos[k - k0], b.ptrs[k], len);
+}
+
+// The page-locked host ranges the library knows (crc32c_host_alloc,
+// crc32c_host_register), by first address, each with the device address of its
+// first byte: a host span's device view is one O(log R) lookup under a shared
+// lock, where the runtime's own answer costs two calls.
+class PinRegistry {
+  public:
+    void record(const void *p, uint64_t bytes, const void *dv) {
+        std::unique_lock<std::shared_mutex> lk(mu_);
+        ranges_[(uintptr_t)p] = Range{(uintptr_t)p + bytes, (const uint8_t *)dv};
+    }
+    void forget(const void *p) {
+        std::unique_lock<std::shared_mutex> lk(mu_);
+        ranges_.erase((uintptr_t)p);
+    }
+    // The span [p, p + len): inside one recorded range (*dv: its device
+    // view), unknown (it starts in none: the runtime may still know it), or
+    // cut (it starts in one and runs past its end: no kernel may read it).
+    enum class Hit { inside, unknown, cut };
+    Hit view(const void *p, uint64_t len, const uint8_t **dv) const {
+        const uintptr_t a = (uintptr_t)p;
+        std::shared_lock<std::shared_mutex> lk(mu_);
+        auto it = ranges_.upper_bound(a);
+        if (it == ranges_.begin()) return Hit::unknown;
+        --it;
+        if (a >= it->second.end) return Hit::unknown;
+        if (len > it->second.end - a) return Hit::cut;
+        *dv = it->second.dv + (a - it->first);
+        return Hit::inside;
+    }
+
+  private:
+    struct Range {
+        uintptr_t end;      // one past the range's last host byte
+        const uint8_t *dv;  // the device view of its first byte
+    };
+    mutable std::shared_mutex mu_;
+    std::map<uintptr_t, Range> ranges_;
+};
 
 // A host chain fold's staging buffer: the n iovs' CRCs, their lengths, at
 // chain_first_off (8-B aligned) the chains' first indices, then the folded CRCs.

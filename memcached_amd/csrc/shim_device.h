@@ -177,6 +177,11 @@ struct Device {
     // ... with CRC32C_SCRUB_BYTES: a byte stage's bit count and its pinned twin (its masks: rp_mask)
     DevBuf<unsigned long long> sc_nbits;
     PinBuf<unsigned long long> sc_hbits;
+    // crc32c_batch_ptrs: a device batch's rebased offsets, k_ptr_rebase's three
+    // words and their pinned twin
+    DevBuf<uint64_t> ptr_offs;
+    DevBuf<unsigned long long> ptr_red;
+    PinBuf<unsigned long long> ptr_hred;
     // pinned, device-mapped scratch of the host item-image calls
     MapBuf<> pin_stage, pin_ok;
     MapBuf<uint64_t> pin_offs;

@@ -17,6 +17,13 @@ struct crc32c_job {
     // the default stream, e.g. the copy filling the spans, stays ordered first)
     hipEvent_t after = nullptr;
     const uint8_t *dbase = nullptr;  // coalesced jobs: the device view of s.base
+    // pointer jobs (crc32c_ptrs_submit): the caller's batch -- s holds its
+    // lens, len, crc_in, out and n, what launch and finish read of any job --
+    // and each span's device view, translated at submit time (empty: a device
+    // job, or some span is pageable)
+    bool ptr = false;
+    crc32c_ptr_batch pb{};
+    std::vector<const uint8_t *> views;
     bool coalesce = false;
     int rc = CRC32C_OK;
     std::atomic<int> done{0};
@@ -26,6 +33,8 @@ struct crc32c_job {
 namespace {
 
 constexpr uint64_t kQueueSpanMax = 256u << 10;  // longer spans: the job runs alone (planned path)
+int run_ptr_job(Device &d, crc32c_job *j, hipStream_t st);  // shim_ptrs.h
+
 static_assert(sizeof(std::atomic<int>) == sizeof(int) && std::atomic<int>::is_always_lock_free,
               "crc32c_job::done is waited on as a futex word");
 
@@ -124,7 +133,7 @@ struct Queue {
         for (crc32c_job *j : l.jobs) {
             const crc32c_spans &s = j->s;
             for (uint64_t i = 0; i < s.n; ++i, ++k) {
-                addr[k] = (uint64_t)(uintptr_t)(j->dbase + mcrc::span_off(s, i));
+                addr[k] = (uint64_t)(uintptr_t)(j->ptr ? j->views[i] : j->dbase + mcrc::span_off(s, i));
                 len[k] = (uint32_t)mcrc::span_len(s, i);
                 cin[k] = s.crc_in ? s.crc_in[i] : 0u;
             }
@@ -167,8 +176,10 @@ struct Queue {
                 j->after = nullptr;
                 if (e != hipSuccess) return CRC32C_EHIP;
             }
+            if (j->ptr) return run_ptr_job(*d, j, st);
             return device_batch(*d, j->s, j->flags & ~(unsigned)CRC32C_ASYNC, st);
         }
+        if (j->ptr) return run_ptr_job(*d, j, st);
         return run_host_batch(*d, j->s);
     }
 
